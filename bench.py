@@ -18,13 +18,18 @@ step untimed, then exactly K steps between barrier + synchronize on both sides, 
 because this kernel runs AT the package power cap: after an idle period the power controller clamps launches 3..20
 (profiles/r02_step_transient.log) and the clock keeps falling for about a second, so K = 20 steps (25 ms) right behind a few
 warm-up steps measure a burst, not the rate a job sees.  With the default settling `value` is the sustained figure
-(`sustained_settle` holds the >= 2 s run in front of it, `first_steps_after_idle` the burst figure); `--settle-steps 0
---settle-seconds 0` makes the burst the headline.  N = 1 hashes BASELINE config 2's own stream (default_rng(20240101) in
-50 000-row chunks), uploaded before anything is timed, and - where the host has >= 12 cores - compares ALL of
-its keys with the reference-literal loop; N > 1 carries `per_gpu_rows` and `single_gpu_same_shard` (rank 0 alone on its
-shard) so that an efficiency is N-GPU rate / (N x that).
+(`sustained_settle` holds the >= 2 s run in front of it, with `--full` `first_steps_after_idle` the burst figure);
+`--settle-steps 0 --settle-seconds 0` makes the burst the headline.  N = 1 hashes BASELINE config 2's own stream
+(default_rng(20240101) in 50 000-row chunks), uploaded before anything is timed, and with `--full` - where the
+host has >= 12 cores - compares ALL of its keys with the reference-literal loop; N > 1 carries `per_gpu_rows` and, with
+`--full`, `single_gpu_same_shard` (rank 0 alone on its shard) so that an efficiency is N-GPU rate / (N x that).
 
-Also in the line (N = 1 unless noted):
+A plain run does only that: set up, settle, time the K steps, print a short line (the headline, its configuration, the
+figures of `roofline` - taken from the timed steps themselves - and the last step's counters: `plain_line`).  `--dump-outputs DIR` then writes what the last timed step computed - rank 0's band keys - as float32
+`DIR/keys.npy` of the rows `DIR/rows.npy` (float64) names: a fixed sample of DUMP_ROWS rows (default_rng(DUMP_SEED)),
+at most 36 MB; the same arguments give the same inputs from run to run.  Everything else is `--full`.
+
+Also in the line with `--full` (N = 1 unless noted):
   roofline      the dominant kernel (stage 1 of the split pass, sig16_kernel), timed with HIP events that ride on its
                 dispatch packets inside the timed region, priced against the LARGER of its two floors - the bf16
                 matrix roof (it executes 3 bf16 MFMAs per algorithmic multiply-add) - with the HBM view beside it;
@@ -66,6 +71,7 @@ PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: dense f32 matrix peak (spe
 PEAK_HBM_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.29 TB/s measured copy)
 PEAK_BF16_MFMA_TFLOPS = 2500.0 # MI355X_MICROARCH.md: dense bf16 matrix peak
 CONFIG4_TOTAL_ROWS = 10_000_000
+DUMP_ROWS, DUMP_SEED = 262_144, 0   # --dump-outputs: rows of the last step's keys written (a fixed sample of larger batches)
 
 
 def pmc_traffic(kernel: str, field: str, units: float):
@@ -115,6 +121,11 @@ def parse():
                     help="rendezvous, one barrier and the JSON line only - no GPU work (exercises the launcher on a CPU box)")
     ap.add_argument("--backend", default=os.environ.get("LSHRS_BENCH_BACKEND", "nccl"),
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for rehearsals on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the burst and single-GPU figures, the parity check against the oracle, "
+                         "the extras, the CPU baselines, the rerank, config 5 and the floors (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float32/float64; a fixed sample of rows)")
     return ap.parse_args()
 
 
@@ -369,7 +380,7 @@ def main() -> None:
 
     hasher.kernel_events = []          # (the warm-up steps are steps like the timed ones: their event ring is built here)
     after_idle = None
-    if args.settle_steps > 0:
+    if args.full and args.settle_steps > 0:
         # what K steps right behind W warm-up steps measure when the chip comes from idle (round 1's line): reported
         # beside the settled figure, and part of the settling
         for _ in range(args.warmup):
@@ -389,7 +400,7 @@ def main() -> None:
     # scaling efficiency needs (N-GPU rate / (N x this)); the joint run follows.  (The N = 1 line is BASELINE config 2, 1 M
     # rows: another batch, with another last-round share.)
     single_same_shard = None
-    if distributed:
+    if distributed and args.full:
         barrier()
         if rank == 0:
             for _ in range(args.settle_steps):
@@ -427,6 +438,14 @@ def main() -> None:
         gathered = [torch.zeros(1, dtype=torch.float64, device=cdev) for _ in range(world)]
         dist.all_gather(gathered, torch.tensor([my_ms], dtype=torch.float64, device=cdev))
         per_rank_ms = [float(g.item()) for g in gathered]
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the (rows, bands, band bytes) uint8 keys of a fixed sample
+        # of rows, as float32 (bytes are exact in it), beside the row numbers - before anything below hashes into `keys` again
+        rows_d = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+        sample = keys[torch.from_numpy(rows_d).to(dev)].cpu().numpy()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "keys.npy"), sample.astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "rows.npy"), rows_d.astype(np.float64))
 
     # every launch of the timed region: (stage-1 ms, None, rows, stage-2 ms) from events riding on the dispatches
     split = bool(events) and all(e[3] is not None for e in events)
@@ -442,7 +461,7 @@ def main() -> None:
 
     # ---------------- parity of what was just measured: EVERY rank, max-reduced ----------------
     parity = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         from oracle.parallel import SharedVectors, hash_shared_literal_packed
 
         hasher.hash_device(x, out=keys)
@@ -539,7 +558,7 @@ def main() -> None:
             "parity_check": parity,
         }
 
-    extras = rank == 0 and world == 1 and not args.no_extras
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras
     if extras:
         for name, fn in (
             ("sustained", lambda: bench_sustained(torch, hasher, x, keys, args.sustained_seconds, barrier)),
@@ -578,7 +597,7 @@ def main() -> None:
                                    "value_over_synchronous": two["value"] / result["value"],
                                    "entry_point": two.get("entry_point"), "keys_equal": two.get("keys_equal"),
                                    "note": "sustained.two_streams, repeated at the top level; `value` stays the synchronous step"}
-    elif world > 1 and not args.no_extras:
+    elif args.full and world > 1 and not args.no_extras:
         # host-fed ingest on every rank at once: what the node's PCIe + host memory give N ranks together
         def max_over_ranks(seconds):
             t = torch.tensor([seconds], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
@@ -646,7 +665,7 @@ def main() -> None:
                 result.setdefault("e2e_ingest", {})["error"] = f"{type(exc).__name__}: {exc}"
 
     # ---------------- CPU baseline (rank 0, N=1 only) ----------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.lshrs_oracle import hash_batch_literal_packed
 
         m = min(n, args.cpu_sample_rows)
@@ -681,7 +700,7 @@ def main() -> None:
         }
 
     # ---------------- second metric: cosine rerank (config 3), N=1 only ----------------
-    if rank == 0 and world == 1 and not args.no_rerank:
+    if args.full and rank == 0 and world == 1 and not args.no_rerank:
         result["rerank"] = bench_rerank(torch, dev, x, np, not args.no_cpu_baseline)
 
     # ---------------- config 5 (needs the memory of the config-2 batch back) ----------------
@@ -693,14 +712,27 @@ def main() -> None:
         except Exception as exc:  # noqa: BLE001
             result["c5"] = {"error": f"{type(exc).__name__}: {exc}"}
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         result["floors"] = floors(result)
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        os.write(real_stdout, (json.dumps(result) + "\n").encode())
+        os.write(real_stdout, (json.dumps(result if args.full else plain_line(result)) + "\n").encode())
     os.close(real_stdout)
+
+
+def plain_line(result) -> dict:
+    """The line of a plain run: the headline with what places it (workload, configuration, the roofline's figures, the last
+    step's counters), short enough to be read whole; the notes, the settling run and the audit totals are in the --full line."""
+    out = {k: result[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "settle_steps", "settle_seconds",
+                                  "per_gpu_rows", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
+    out["config"] = {k: result["config"][k] for k in ("workload", "world_size", "backend", "per_rank_ms_per_step", "tie_break_engine",
+                                                      "tau1_ulps", "step_entry_point")}
+    out["roofline"] = {k: v for k, v in result["roofline"].items()
+                       if k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "kernel_ms_mean", "step_over_stage1")}
+    out["stats_last_step"] = result["stats_last_step"]
+    return out
 
 
 def sample_power(device_index: int):

@@ -330,7 +330,15 @@ class _ReplayPaths:
             stats["margin_escalations"] = self.margin_escalations
             return False
         if ev is not None and self.kernel_events is not None:
-            self.kernel_events.append((ev[0].elapsed_time(ev[1]), None, n, ev[2].elapsed_time(ev[3])))
+            try:
+                ms1, ms2 = ev[0].elapsed_time(ev[1]), ev[2].elapsed_time(ev[3])
+            except RuntimeError:
+                # the host saw the pass end through the `done` word, which can come before the runtime reports the
+                # launch's timing events complete: wait for them (timing runs only), then read the durations
+                for e in ev:
+                    e.synchronize()
+                ms1, ms2 = ev[0].elapsed_time(ev[1]), ev[2].elapsed_time(ev[3])
+            self.kernel_events.append((ms1, None, n, ms2))
         stats["tie_entries"] = ties
         stats["tie_pairs"] = ties          # (tied PROJECTIONS here: each decided by the replayed host order)
         stats["flagged"] = flagged         # projections inside the stage-1 window: every one decided by stage 2

@@ -19,6 +19,8 @@ inputs, and stores inputs' seeds + the reference's outputs as data:
   g6_autoconfig.json    get_optimal_config table
   g7_saved_index/       an index directory written by the reference's save_to_disk
   g8_queries_768.json   100 queries against 3 000 clustered 768-d vectors (num_perm 256): query() results
+  g2_blas_fingerprint.json   what the BLAS that computed G2 returns for plane @ x (not from the reference)
+  g10_parquet_loader.npz     the reference's Parquet loader: batches of ids and vectors
 
 Fixtures are data only (inputs are regenerated from seeds by the tests).
 """
@@ -297,10 +299,47 @@ def main() -> None:
                      redis_password="hunter2", redis_prefix="pfx", similarity_threshold=0.6)
         idx7.save_to_disk(g7)
 
+    g2_blas_fingerprint()
+    g10_parquet_loader()
     print("golden fixtures written to", OUT)
+
+
+def g2_blas_fingerprint() -> None:
+    """G2's companion: what the BLAS that computed G2 returns for ``plane @ x`` (tests/test_oracle_golden.py,
+    blas_fingerprint) - a host whose BLAS gives the same must reproduce every G2 row."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from tests.test_oracle_golden import blas_fingerprint
+
+    json.dump({"numpy": np.__version__, "plane_at_x_sha256": blas_fingerprint()},
+              open(os.path.join(OUT, "g2_blas_fingerprint.json"), "w"), indent=1)
+
+
+def g10_parquet_loader() -> None:
+    """G10: the reference's iter_parquet_vectors over 1 200 rows of 16 float64 values (default_rng(6)) with int32 ids,
+    row groups of 500, batches of 400 (tests/test_parquet_loader.py)."""
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+
+    ref = _load("ref_parquet_loader", REF + "/io/parquet.py")
+    rng = np.random.default_rng(6)
+    table = pa.table({"index": pa.array(np.arange(1200), type=pa.int32()),
+                      "vector": pa.array(rng.standard_normal((1200, 16)).tolist(), type=pa.list_(pa.float64()))})
+    g10 = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "v.parquet")
+        pq.write_table(table, path, row_group_size=500)
+        for k, (ids, vectors) in enumerate(ref.iter_parquet_vectors(path, batch_size=400)):
+            assert all(type(i) is int for i in ids) and vectors.dtype == np.float32
+            g10[f"batch{k}_ids"] = np.asarray(ids, dtype=np.int64)
+            g10[f"batch{k}_vectors"] = vectors
+    np.savez_compressed(os.path.join(OUT, "g10_parquet_loader.npz"), **g10)
 
 
 if __name__ == "__main__":
     if not os.path.isdir(REF):
         sys.exit("reference checkout not present; fixtures can only be regenerated in the build container")
-    main()
+    if sys.argv[1:]:            # only the named recipes, e.g. g2_blas_fingerprint g10_parquet_loader
+        for name in sys.argv[1:]:
+            globals()[name]()
+    else:
+        main()

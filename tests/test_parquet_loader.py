@@ -1,9 +1,8 @@
 """Parquet loader fast path against the literal restatement of the reference loader
-(oracle/parquet_oracle.py), and that restatement against the real reference where it is present.  CPU only."""
+(oracle/parquet_oracle.py), and that restatement against what the real reference loader yielded (tests/golden).  CPU only."""
 
 from __future__ import annotations
 
-import importlib.util
 import os
 import time
 
@@ -81,19 +80,17 @@ def test_errors_match_the_reference(tmp_path):
         list(iter_parquet_vectors(good, vector_column="embedding"))
 
 
-def test_restatement_equals_the_real_reference_loader(tmp_path):
-    ref_file = "/root/reference/lshrs/io/parquet.py"
-    if not os.path.exists(ref_file):
-        pytest.skip("reference checkout not present (only in the build container)")
-    spec = importlib.util.spec_from_file_location("ref_parquet_loader", ref_file)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+def test_restatement_equals_the_real_reference_loader(tmp_path, golden_dir):
+    """Against what the reference's own iter_parquet_vectors yielded for this file (tests/golden/make_golden.py, G10)."""
+    g = np.load(os.path.join(golden_dir, "g10_parquet_loader.npz"))
+    ref = [(g[f"batch{k}_ids"].tolist(), g[f"batch{k}_vectors"]) for k in range(len(g.files) // 2)]
+    assert len(ref) == 3
     rng = np.random.default_rng(6)
     ids = pa.array(np.arange(1200), type=pa.int32())
     col = pa.array(rng.standard_normal((1200, 16)).tolist(), type=pa.list_(pa.float64()))
     path = write(tmp_path / "v.parquet", ids, col, row_group_size=500)
-    same(iter_parquet_vectors_literal(path, batch_size=400), ref.iter_parquet_vectors(path, batch_size=400))
-    same(iter_parquet_vectors(path, batch_size=400), ref.iter_parquet_vectors(path, batch_size=400))
+    same(iter_parquet_vectors_literal(path, batch_size=400), ref)
+    same(iter_parquet_vectors(path, batch_size=400), ref)
 
 
 def test_create_signatures_uses_the_fast_loader_and_is_faster(tmp_path, monkeypatch):

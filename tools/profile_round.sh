@@ -11,7 +11,7 @@ stats() {   # stats <name> <command...>: kernel trace + stats of one command, it
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name" -- "$@" > "$OUT/${name}_under_rocprof.json" 2> "$OUT/${name}_under_rocprof.err"
   cp "$(ls "$OUT/$name"/*/*kernel_stats.csv | head -1)" "$OUT/${name}_kernel_stats.csv" 2>/dev/null
 }
-stats bench python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extras
+stats bench python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras
 python3 tools/trace_steps.py "$OUT/bench" > "$OUT/bench_kernel_trace_timed_steps.json" 2>> "$OUT/bench_under_rocprof.err"
 stats c5 python3 bench.py --only c5 --no-check
 stats rerank python3 bench.py --only rerank --no-cpu-baseline
