@@ -523,6 +523,24 @@ int lshrs_cosine_ragged_f32(const float* corpus, int64_t m, int64_t ldc, int32_t
                             const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
                             float* scores, int32_t* err, void* stream);
 
+/* lshrs_cosine_batch_f32 / lshrs_cosine_ragged_f32 on a corpus stored in 16 bits: bfloat16 (_bf16) or IEEE binary16 (_f16)
+ * bit patterns, (m, dim) with row stride ldc in ELEMENTS.  Every element is converted to f32 exactly (bf16: its bits are the
+ * high half of the f32; f16: subnormals included, nothing flushed) and the scores are computed in f32 against the f32 queries
+ * (f32 FMAs, no 16-bit product): the f32 entries' scores on the upcast corpus, up to the order of the f32 sums.  Queries,
+ * candidates, scores, status, qstatus, err and the limits are those of the f32 entries. */
+int lshrs_cosine_batch_bf16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                            const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus,
+                            void* stream);
+int lshrs_cosine_batch_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                           const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus,
+                           void* stream);
+int lshrs_cosine_ragged_bf16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                             const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
+                             float* scores, int32_t* err, void* stream);
+int lshrs_cosine_ragged_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                            const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
+                            float* scores, int32_t* err, void* stream);
+
 /* Per query the first keep[qi] candidates in descending score (ties: ascending position in the list; NaN last - the order of
  * lshrs_topk_desc_f32) into the compact arrays out_ids / out_scores at out_off[qi]; lists and scores at pair_off[qi], ucount[qi]
  * long; a list longer than max_candidates (<= LSHRS_QUERY_MAX_PAIRS: the LDS network) is left to the caller (lshrs_topk_desc_f32

@@ -175,6 +175,11 @@ def _declare(lib: ctypes.CDLL) -> None:
     # (corpus, m, ldc, dim, queries, q, cand_rows, row_off, row_cnt, total, scores, err, stream)
     lib.lshrs_cosine_ragged_f32.argtypes = [vp, i64, i64, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp]
     lib.lshrs_cosine_ragged_f32.restype = c.c_int
+    # the same two forms on a corpus of 16-bit elements (ldc in elements): bf16 / f16 converted exactly to f32
+    for dt in ("bf16", "f16"):
+        batch, ragged = getattr(lib, "lshrs_cosine_batch_" + dt), getattr(lib, "lshrs_cosine_ragged_" + dt)
+        batch.argtypes, batch.restype = lib.lshrs_cosine_batch_f32.argtypes, c.c_int
+        ragged.argtypes, ragged.restype = lib.lshrs_cosine_ragged_f32.argtypes, c.c_int
     # (cand_ids, scores, pair_off, ucount, keep, out_off, q, max_candidates, out_ids, out_scores, done_host, epoch, stream)
     lib.lshrs_query_rank_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
     lib.lshrs_query_rank_f32.restype = c.c_int
@@ -220,6 +225,10 @@ EXPORTS = (
     "lshrs_query_collide_big_i64",
     "lshrs_query_one_u8",
     "lshrs_cosine_ragged_f32",
+    "lshrs_cosine_batch_bf16",
+    "lshrs_cosine_batch_f16",
+    "lshrs_cosine_ragged_bf16",
+    "lshrs_cosine_ragged_f16",
     "lshrs_query_rank_f32",
     "lshrs_pipe_create",
     "lshrs_pipe_destroy",

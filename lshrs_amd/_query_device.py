@@ -6,8 +6,8 @@ Per query the reference reads one bucket per band, counts in a dict how often ev
 download (ids, scores, bounds):
 
   signature pass -> ``lshrs_query_lookup_u8`` (bisection in the device-resident bucket arrays) -> scan ->
-  ``lshrs_query_collide_*`` (sort / count / order inside a workgroup's LDS) -> [``lshrs_cosine_ragged_f32`` on the resident
-  corpus] -> ``lshrs_query_rank_f32`` (order by score, cut to top-p / top-k, compact)
+  ``lshrs_query_collide_*`` (sort / count / order inside a workgroup's LDS) -> [``lshrs_cosine_ragged_{f32,bf16,f16}`` on the
+  resident corpus] -> ``lshrs_query_rank_f32`` (order by score, cut to top-p / top-k, compact)
 
 ``DeviceBuckets`` mirrors the array segments of a store (``InMemoryStorage.array_segments``) in device memory: uploaded
 the first time a query meets them, kept until the store replaces them.  Stores that only answer ``get_bucket`` (the
@@ -23,6 +23,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _native
+from .similarity import corpus_entry
 from .windows import _U
 
 __all__ = ["DeviceBuckets", "TooLarge", "candidates_from_index", "candidates_from_pairs", "rank_and_cut"]
@@ -228,8 +229,9 @@ def rank_and_cut(lists: _Lists, top_k: Optional[int], top_p: Optional[float], *,
                  cand_rows=None) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
     """The ranked, cut answer of every query as arrays ``(ids, scores or None, bounds)``: query i's ids are
     ``ids[bounds[i]:bounds[i + 1]]``.  ``top_p`` None: the collision order, first ``top_k`` (lshrs/core/main.py:619-625).
-    Else the candidates scored against ``corpus`` (device (m, dim) float32; row = ``cand_rows`` entry, default the id
-    itself), ordered by score, cut to ``max(1, ceil(n * top_p))`` and ``top_k`` (:646-657)."""
+    Else the candidates scored against ``corpus`` (device (m, dim) float32, bfloat16 or float16 -
+    ``similarity.corpus_entry``; row = ``cand_rows`` entry, default the id itself), ordered by score, cut to
+    ``max(1, ceil(n * top_p))`` and ``top_k`` (:646-657)."""
     torch = _native.require_gpu()
     lib = _native.load()
     dev, nq = lists.dev, lists.nq
@@ -242,13 +244,14 @@ def rank_and_cut(lists: _Lists, top_k: Optional[int], top_p: Optional[float], *,
                            top_p=-1.0 if top_p is None else float(top_p), keep_out=keep)
         scores = err = None
         if top_p is not None and lists.total:
+            entry = corpus_entry(corpus, "ragged")
             rows = lists.cand_ids if cand_rows is None else cand_rows
             scores = torch.empty(max(1, lists.total), dtype=torch.float32, device=dev)
             err = torch.zeros(1, dtype=torch.int32, device=dev)
-            _native.check(lib.lshrs_cosine_ragged_f32(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)),
-                                                      int(corpus.shape[1]), queries_dev.data_ptr(), nq, rows.data_ptr(),
-                                                      lists.pair_off.data_ptr(), lists.ucount.data_ptr(), lists.total,
-                                                      scores.data_ptr(), err.data_ptr(), stream), "lshrs_cosine_ragged_f32")
+            _native.check(getattr(lib, entry)(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)),
+                                              int(corpus.shape[1]), queries_dev.data_ptr(), nq, rows.data_ptr(),
+                                              lists.pair_off.data_ptr(), lists.ucount.data_ptr(), lists.total,
+                                              scores.data_ptr(), err.data_ptr(), stream), entry)
         bounds = out_off.cpu().numpy()                # (waits for the scan - and whatever is in front of it - only: the rerank runs on)
         kept = int(bounds[-1])
         # ids and scores side by side in ONE block: one copy back
@@ -354,6 +357,8 @@ class OneQuery:
             raise TooLarge("member ids do not fit the item layout")
         dev = self.dev
         p = self.ptr
+        rerank = top_p >= 0.0
+        entry = corpus_entry(corpus, "ragged", dim) if rerank else None     # (before anything is enqueued)
         with self.lock, torch.cuda.device(dev):
             raw = torch._C._cuda_getCurrentRawStream(dev.index)
             nslots = nb * nseg
@@ -370,15 +375,14 @@ class OneQuery:
             self.epoch = epoch = self.epoch % 0x7FFFFFF0 + 1
             rc = lib.lshrs_sig_hash_small_replay_f32(p["x"], 1, self.ldx, ws.data_ptr(), nb, hasher.rows_per_band, dim, p["keys"],
                                                      p["flags"], p["hash_counters"], float(8.0 * _U), model, None, 0, raw)
-            rerank = top_p >= 0.0
             rc = rc or lib.lshrs_query_one_u8(p["keys"], nb, bb, desc.data_ptr() if desc is not None else None, nseg,
                                               s_start.data_ptr(), s_len.data_ptr(), s_off.data_ptr(), self.CAP, int(top_k),
                                               float(top_p), 1 if rerank else 0, p["pair_off"], p["cand"], p["ucount"], p["keep"],
                                               p["out_off"], p["ids"], p["done"], epoch, p["x"] if rerank else None,
                                               p["x_dev"] if rerank else None, dim if rerank else 0, raw)
             if rerank and not rc:
-                rc = lib.lshrs_cosine_ragged_f32(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)), dim, p["x_dev"], 1,
-                                                 p["cand"], p["pair_off"], p["ucount"], 4096, p["scores"], p["err"], raw)
+                rc = getattr(lib, entry)(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)), dim, p["x_dev"], 1,
+                                         p["cand"], p["pair_off"], p["ucount"], 4096, p["scores"], p["err"], raw)
                 rc = rc or lib.lshrs_query_rank_f32(p["cand"], p["scores"], p["pair_off"], p["ucount"], p["keep"], p["zero_off"], 1,
                                                     self.CAP, p["ids"], p["scores_out"], p["done"], epoch, raw)
             if rc:

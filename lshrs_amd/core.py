@@ -37,6 +37,7 @@ from ._gcpause import gc_paused as _gc_paused
 from .bandrows import get_optimal_config
 from .hasher import LSHHasher
 from .packed_ops import bucket_csr as _bucket_csr
+from .similarity import corpus_entry
 from .similarity import rerank_padded_arrays as _rerank_padded
 from .similarity import top_k_cosine
 from .storage import BucketOperation, default_storage
@@ -473,9 +474,9 @@ class LSHRS:
         rerank = top_p is not None and not bad_p
         corpus = self._corpus
         if rerank:
-            torch = __import__("torch")
-            if not (isinstance(corpus, torch.Tensor) and corpus.is_cuda and corpus.dtype == torch.float32 and corpus.dim() == 2
-                    and int(corpus.shape[1]) == self._dim and corpus.stride(1) == 1):
+            try:
+                corpus_entry(corpus, "ragged", self._dim)       # a device corpus the rerank reads as it is (float32 / bf16 / f16)
+            except ValueError:
                 return None
         st = self._storage
         if isinstance(st, _DeferredStorage):
@@ -535,9 +536,12 @@ class LSHRS:
         return list(self.query(vector, top_k=None, top_p=p))  # type: ignore[arg-type]
 
     def set_corpus(self, corpus) -> None:
-        """Attach the indexed vectors as a device-resident ``(m, dim)`` float32 tensor whose row ``i`` is the vector of id
-        ``i``: ``query`` / ``get_above_p`` / ``query_many`` then gather their candidates from it on the device instead of
-        calling ``vector_fetch_fn`` (lshrs/core/main.py:629-646 fetches and stacks them on the host).  ``None`` detaches."""
+        """Attach the indexed vectors as a device-resident ``(m, dim)`` float32, bfloat16 or float16 tensor whose row ``i``
+        is the vector of id ``i``: ``query`` / ``get_above_p`` / ``query_many`` then gather their candidates from it on the
+        device instead of calling ``vector_fetch_fn`` (lshrs/core/main.py:629-646 fetches and stacks them on the host).
+        16-bit rows are converted to float32 exactly inside the rerank: the scores are those of ``corpus.float()`` (the
+        reference's ``np.asarray(fetch(ids), dtype=np.float32)``), at half the memory and half the bytes gathered.
+        ``None`` detaches."""
         if corpus is not None and (getattr(corpus, "ndim", 0) != 2 or int(corpus.shape[1]) != self._dim):
             raise ValueError(f"corpus must have shape (m, {self._dim})")
         self._corpus = corpus
@@ -552,9 +556,10 @@ class LSHRS:
 
         ``vectors``: ``(n, dim)`` array-like as in the reference - or a torch tensor that already lives on a GPU (round 6: the
         queries then never cross the link; 10 000 x 768 are 30 MB = 0.7 of the 2.7 ms a reranked batch takes).
-        ``corpus``: optional device-resident ``(m, dim)`` float32 tensor whose row ``i`` is the vector of id
-        ``i`` (default: what :meth:`set_corpus` attached); with it the candidates are gathered on the device and
-        ``vector_fetch_fn`` is not called.
+        ``corpus``: optional device-resident ``(m, dim)`` float32, bfloat16 or float16 tensor whose row ``i`` is the vector
+        of id ``i`` (default: what :meth:`set_corpus` attached); with it the candidates are gathered on the device and
+        ``vector_fetch_fn`` is not called (16-bit rows are converted to float32 exactly: the scores of ``corpus.float()``;
+        another dtype raises ``ValueError``).
         ``return_arrays``: ``(ids, scores, bounds)`` instead of lists - query ``i``'s answer is ``ids[bounds[i]:bounds[i + 1]]``
         (int64) with ``scores[...]`` (float32; ``None`` without ``top_p``): no Python object per result.
         ``engine``: "auto" (the device path wherever the hasher is the HIP one; a batch with a candidate list beyond the
@@ -648,12 +653,11 @@ class LSHRS:
                 return np.empty(0, np.int64), np.empty(0, np.float32), np.zeros(nq + 1, np.int64)
             if corpus is not None:
                 table = corpus if isinstance(corpus, torch.Tensor) else qd.upload(torch, np.asarray(corpus, dtype=np.float32), dev)
-                if table.dtype != torch.float32 or table.dim() != 2 or int(table.shape[1]) != self._dim:
-                    raise ValueError(f"corpus must be a float32 tensor of shape (m, {self._dim})")
                 if not table.is_cuda:
                     table = table.to(dev)
-                if table.stride(1) != 1:
+                if table.dim() == 2 and table.stride(1) != 1:
                     table = table.contiguous()
+                corpus_entry(table, "ragged", self._dim)            # (raises a ValueError naming the dtypes it takes)
                 return qd.rank_and_cut(lists, top_k, top_p, queries_dev=x, corpus=table)
             # no resident corpus: the candidates' vectors come from the caller's fetch function, list by list as the reference
             # asks for them (main.py:629), and travel to the device as one table

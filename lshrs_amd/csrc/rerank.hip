@@ -6,6 +6,8 @@
 // ABI and reference citations: include/lshrs_hip.h.  Design notes: DESIGN.md.
 #include "lshrs_common.h"
 
+#include <type_traits>
+
 using namespace lshrs;
 
 namespace {
@@ -14,10 +16,37 @@ namespace {
 // its candidates); the query sits in LDS, each wave streams whole candidate rows (16 B per
 // lane per load, four rows in flight), reduces dot and ||c||^2 across the wave, and lane 0
 // writes dot / (||c|| * ||q||).
+// A corpus stored in 16 bits (bf16 / f16) takes the same kernel: each element is converted to
+// f32 exactly in registers, every product and sum stays an f32 FMA against the f32 query; a
+// 16-B load holds 8 elements, and eight rows are in flight to keep the bytes per wave of f32
+// (their indices and row pointers in scalar registers: 114 VGPRs, four waves per SIMD).
 // ------------------------------------------------------------------------------------------
 constexpr int kCosThreads = 256;
 constexpr int kCosWaves = kCosThreads / 64;
 constexpr int kCosInflight = 4;
+
+struct Bf16 {};   // element tags of a 16-bit corpus (rows of uint16_t)
+struct F16 {};
+
+// per element type: what a row holds, rows in flight per wave, elements per 16-B load
+template <typename E> struct CosElem {
+  using T = uint16_t;
+  static constexpr int kInflight = 2 * kCosInflight;
+  static constexpr int kVec = 8;
+};
+template <> struct CosElem<float> {
+  using T = float;
+  static constexpr int kInflight = kCosInflight;
+  static constexpr int kVec = 4;
+};
+
+// exact conversions: the element in the low / high half of a dword, and a lone 16-bit element
+__device__ __forceinline__ float elem_lo(Bf16, uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float elem_hi(Bf16, uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+__device__ __forceinline__ float elem_lo(F16, uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)w); }
+__device__ __forceinline__ float elem_hi(F16, uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
+template <typename E>
+__device__ __forceinline__ float elem(uint16_t bits) { return elem_lo(E{}, bits); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -28,9 +57,10 @@ __device__ __forceinline__ float wave_sum(float v) {
 // RAGGED (ABI 7, lshrs_cosine_ragged_f32): query qi has row_cnt[qi] candidates, listed - and scored - at row_off[qi] of the
 // flat cand_idx / scores arrays (the candidate lists of a batch of LSH queries, lshrs/core/main.py:629-646); what is wrong with
 // a candidate is OR-ed into err[0] (1 zero norm, 2 index outside the corpus) instead of a status byte per candidate.
-template <bool ALIGNED, bool RAGGED>
-__global__ __launch_bounds__(kCosThreads) void cosine_kernel(const float* __restrict__ corpus, int64_t m, int64_t ldc,
-                                                             int dim, const float* __restrict__ queries,
+// E: float, Bf16 or F16 - the corpus's element type (ldc in elements); queries, scores and status are f32 / u8 for all three.
+template <typename E, bool ALIGNED, bool RAGGED>
+__global__ __launch_bounds__(kCosThreads) void cosine_kernel(const typename CosElem<E>::T* __restrict__ corpus, int64_t m,
+                                                             int64_t ldc, int dim, const float* __restrict__ queries,
                                                              const int64_t* __restrict__ cand_idx, int c, int slices,
                                                              float* __restrict__ scores, uint8_t* __restrict__ status,
                                                              uint8_t* __restrict__ qstatus,
@@ -39,7 +69,9 @@ __global__ __launch_bounds__(kCosThreads) void cosine_kernel(const float* __rest
   extern __shared__ __attribute__((aligned(16))) float qlds[];  // dim floats (+ pad to 4) + kCosWaves partials
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wave = tid >> 6;
+  // (16-bit rows: the wave index said to be wave-uniform, so that a wave's candidate indices and row pointers sit in scalar
+  // registers - eight rows in flight then leave the vector registers for the data)
+  const int wave = std::is_same_v<E, float> ? tid >> 6 : __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qi = blockIdx.x / slices;
   const int slice = blockIdx.x % slices;
   int64_t obase = (int64_t)qi * c;
@@ -68,16 +100,18 @@ __global__ __launch_bounds__(kCosThreads) void cosine_kernel(const float* __rest
   if (slice == 0 && tid == 0 && qstatus != nullptr) qstatus[qi] = (qnorm == 0.f) ? 1 : 0;
   if (RAGGED && slice == 0 && tid == 0 && err != nullptr && qnorm == 0.f) atomicOr(err, 4);
 
-  // candidates of this slice, dealt to waves in groups of kCosInflight
+  // candidates of this slice, dealt to waves in groups of kInflight
+  using T = typename CosElem<E>::T;
+  constexpr int kInflight = CosElem<E>::kInflight;
   const int per_slice = (c + slices - 1) / slices;
   const int c_begin = slice * per_slice;
   const int c_end = min(c, c_begin + per_slice);
 
-  for (int base = c_begin + wave * kCosInflight; base < c_end; base += kCosWaves * kCosInflight) {
-    const float* rowp[kCosInflight];
-    int st[kCosInflight];
+  for (int base = c_begin + wave * kInflight; base < c_end; base += kCosWaves * kInflight) {
+    const T* rowp[kInflight];
+    int st[kInflight];
 #pragma unroll
-    for (int u = 0; u < kCosInflight; ++u) {
+    for (int u = 0; u < kInflight; ++u) {
       const int ci = base + u;
       int64_t idx = 0;
       st[u] = 3;  // 3 = not a candidate (past the end)
@@ -87,37 +121,73 @@ __global__ __launch_bounds__(kCosThreads) void cosine_kernel(const float* __rest
       }
       rowp[u] = corpus + (st[u] == 0 ? idx : 0) * ldc;
     }
-    float dot[kCosInflight], nn[kCosInflight];
+    float dot[kInflight], nn[kInflight];
 #pragma unroll
-    for (int u = 0; u < kCosInflight; ++u) { dot[u] = 0.f; nn[u] = 0.f; }
+    for (int u = 0; u < kInflight; ++u) { dot[u] = 0.f; nn[u] = 0.f; }
 
-    if (ALIGNED) {
-      for (int k = lane * 4; k < dim; k += 256) {
-        const f32x4 qx = *reinterpret_cast<const f32x4*>(qlds + k);
-        f32x4 cx[kCosInflight];
+    if constexpr (std::is_same_v<E, float>) {
+      if (ALIGNED) {
+        for (int k = lane * 4; k < dim; k += 256) {
+          const f32x4 qx = *reinterpret_cast<const f32x4*>(qlds + k);
+          f32x4 cx[kInflight];
 #pragma unroll
-        for (int u = 0; u < kCosInflight; ++u) cx[u] = *reinterpret_cast<const f32x4*>(rowp[u] + k);
+          for (int u = 0; u < kInflight; ++u) cx[u] = *reinterpret_cast<const f32x4*>(rowp[u] + k);
 #pragma unroll
-        for (int u = 0; u < kCosInflight; ++u)
+          for (int u = 0; u < kInflight; ++u)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            dot[u] = __builtin_fmaf(cx[u][e], qx[e], dot[u]);
-            nn[u] = __builtin_fmaf(cx[u][e], cx[u][e], nn[u]);
+            for (int e = 0; e < 4; ++e) {
+              dot[u] = __builtin_fmaf(cx[u][e], qx[e], dot[u]);
+              nn[u] = __builtin_fmaf(cx[u][e], cx[u][e], nn[u]);
+            }
+        }
+      } else {
+        for (int k = lane; k < dim; k += 64) {
+          const float qx = qlds[k];
+#pragma unroll
+          for (int u = 0; u < kInflight; ++u) {
+            const float cx = rowp[u][k];
+            dot[u] = __builtin_fmaf(cx, qx, dot[u]);
+            nn[u] = __builtin_fmaf(cx, cx, nn[u]);
           }
+        }
       }
     } else {
-      for (int k = lane; k < dim; k += 64) {
-        const float qx = qlds[k];
+      if (ALIGNED) {
+        // 8 elements per lane per load (dim, ldc multiples of 8, 16-B aligned base): element 2e / 2e+1 of the 8 are the
+        // low / high half of dword e, summed in element order
+        for (int k = lane * 8; k < dim; k += 512) {
+          const f32x4 q0 = *reinterpret_cast<const f32x4*>(qlds + k);
+          const f32x4 q1 = *reinterpret_cast<const f32x4*>(qlds + k + 4);
+          const float qx[8] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
+          u32x4 cx[kInflight];
 #pragma unroll
-        for (int u = 0; u < kCosInflight; ++u) {
-          const float cx = rowp[u][k];
-          dot[u] = __builtin_fmaf(cx, qx, dot[u]);
-          nn[u] = __builtin_fmaf(cx, cx, nn[u]);
+          for (int u = 0; u < kInflight; ++u) cx[u] = *reinterpret_cast<const u32x4*>(rowp[u] + k);
+#pragma unroll
+          for (int u = 0; u < kInflight; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float a = elem_lo(E{}, cx[u][e]), b = elem_hi(E{}, cx[u][e]);
+              dot[u] = __builtin_fmaf(a, qx[2 * e], dot[u]);
+              nn[u] = __builtin_fmaf(a, a, nn[u]);
+              dot[u] = __builtin_fmaf(b, qx[2 * e + 1], dot[u]);
+              nn[u] = __builtin_fmaf(b, b, nn[u]);
+            }
+        }
+      } else {
+        // any dim and row stride: one element per lane per load
+        for (int k = lane; k < dim; k += 64) {
+          const float qx = qlds[k];
+#pragma unroll
+          for (int u = 0; u < kInflight; ++u) {
+            const float cx = elem<E>(rowp[u][k]);
+            dot[u] = __builtin_fmaf(cx, qx, dot[u]);
+            nn[u] = __builtin_fmaf(cx, cx, nn[u]);
+          }
         }
       }
     }
 #pragma unroll
-    for (int u = 0; u < kCosInflight; ++u) {
+    for (int u = 0; u < kInflight; ++u) {
       const float d = wave_sum(dot[u]);
       const float s2 = wave_sum(nn[u]);
       if (lane == 0 && st[u] != 3) {
@@ -292,11 +362,12 @@ int lshrs_sort_u64_rows(uint64_t* items, int q, int64_t cpad, hipStream_t s) {
   return -(int)hipGetLastError();
 }
 
-extern "C" {
-
-int lshrs_cosine_batch_f32(const float* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
-                           const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus,
-                           void* stream) {
+namespace {
+// The launchers behind the six lshrs_cosine_{batch,ragged}_{f32,bf16,f16} entries: argument checks (before anything touches a
+// device), slicing and the choice of the aligned path, written once for every corpus element type.
+template <typename E>
+int cosine_batch(const typename CosElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                 const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus, void* stream) {
   if (q == 0 || c == 0) return 0;
   if (corpus == nullptr || queries == nullptr || scores == nullptr || m <= 0 || dim <= 0 || q < 0 || c < 0 || ldc < dim)
     return LSHRS_E_BADARG;
@@ -304,25 +375,27 @@ int lshrs_cosine_batch_f32(const float* corpus, int64_t m, int64_t ldc, int32_t 
   if (cand_idx == nullptr && (int64_t)q * c > m) return LSHRS_E_BADARG;
   // enough workgroups to fill 256 CUs several times over even for a single query
   int slices = 1;
-  const int per_block = kCosWaves * kCosInflight;
+  const int per_block = kCosWaves * CosElem<E>::kInflight;
   while ((int64_t)q * slices < 4096 && (c + slices - 1) / slices > 2 * per_block) slices *= 2;
   if ((int64_t)q * slices > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
-  const bool aligned = (dim % 4 == 0) && (ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(corpus) & 15) == 0);
+  constexpr int kVec = CosElem<E>::kVec;
+  const bool aligned = (dim % kVec == 0) && (ldc % kVec == 0) && ((reinterpret_cast<uintptr_t>(corpus) & 15) == 0);
   const size_t shmem = (size_t)(((dim + 3) & ~3) + kCosWaves) * sizeof(float);
   const dim3 grid((unsigned)((int64_t)q * slices)), block(kCosThreads);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (aligned)
-    hipLaunchKernelGGL((cosine_kernel<true, false>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_idx, c, slices,
+    hipLaunchKernelGGL((cosine_kernel<E, true, false>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_idx, c, slices,
                        scores, status, qstatus, nullptr, nullptr, nullptr);
   else
-    hipLaunchKernelGGL((cosine_kernel<false, false>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_idx, c, slices,
+    hipLaunchKernelGGL((cosine_kernel<E, false, false>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_idx, c, slices,
                        scores, status, qstatus, nullptr, nullptr, nullptr);
   return -(int)hipGetLastError();
 }
 
-int lshrs_cosine_ragged_f32(const float* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
-                            const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
-                            float* scores, int32_t* err, void* stream) {
+template <typename E>
+int cosine_ragged(const typename CosElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                  const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total, float* scores,
+                  int32_t* err, void* stream) {
   if (q == 0 || total == 0) return 0;
   if (corpus == nullptr || queries == nullptr || cand_rows == nullptr || row_off == nullptr || row_cnt == nullptr ||
       scores == nullptr || m <= 0 || dim <= 0 || q < 0 || total < 0 || ldc < dim)
@@ -331,21 +404,61 @@ int lshrs_cosine_ragged_f32(const float* corpus, int64_t m, int64_t ldc, int32_t
   // slices per query from the AVERAGE list (the lists of one batch are alike: a bucket per band each): enough workgroups to
   // fill 256 CUs several times over even for a handful of queries
   int slices = 1;
-  const int per_block = kCosWaves * kCosInflight;
+  const int per_block = kCosWaves * CosElem<E>::kInflight;
   const int64_t avg = (total + q - 1) / q;
   while ((int64_t)q * slices < 4096 && (avg + slices - 1) / slices > 2 * per_block && slices < 1024) slices *= 2;
   if ((int64_t)q * slices > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
-  const bool aligned = (dim % 4 == 0) && (ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(corpus) & 15) == 0);
+  constexpr int kVec = CosElem<E>::kVec;
+  const bool aligned = (dim % kVec == 0) && (ldc % kVec == 0) && ((reinterpret_cast<uintptr_t>(corpus) & 15) == 0);
   const size_t shmem = (size_t)(((dim + 3) & ~3) + kCosWaves) * sizeof(float);
   const dim3 grid((unsigned)((int64_t)q * slices)), block(kCosThreads);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (aligned)
-    hipLaunchKernelGGL((cosine_kernel<true, true>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_rows, 0, slices,
+    hipLaunchKernelGGL((cosine_kernel<E, true, true>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_rows, 0, slices,
                        scores, nullptr, nullptr, row_off, row_cnt, err);
   else
-    hipLaunchKernelGGL((cosine_kernel<false, true>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_rows, 0, slices,
+    hipLaunchKernelGGL((cosine_kernel<E, false, true>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_rows, 0, slices,
                        scores, nullptr, nullptr, row_off, row_cnt, err);
   return -(int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" {
+
+int lshrs_cosine_batch_f32(const float* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                           const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus,
+                           void* stream) {
+  return cosine_batch<float>(corpus, m, ldc, dim, queries, q, cand_idx, c, scores, status, qstatus, stream);
+}
+
+int lshrs_cosine_batch_bf16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                            const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus,
+                            void* stream) {
+  return cosine_batch<Bf16>(corpus, m, ldc, dim, queries, q, cand_idx, c, scores, status, qstatus, stream);
+}
+
+int lshrs_cosine_batch_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                           const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus,
+                           void* stream) {
+  return cosine_batch<F16>(corpus, m, ldc, dim, queries, q, cand_idx, c, scores, status, qstatus, stream);
+}
+
+int lshrs_cosine_ragged_f32(const float* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                            const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
+                            float* scores, int32_t* err, void* stream) {
+  return cosine_ragged<float>(corpus, m, ldc, dim, queries, q, cand_rows, row_off, row_cnt, total, scores, err, stream);
+}
+
+int lshrs_cosine_ragged_bf16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                             const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
+                             float* scores, int32_t* err, void* stream) {
+  return cosine_ragged<Bf16>(corpus, m, ldc, dim, queries, q, cand_rows, row_off, row_cnt, total, scores, err, stream);
+}
+
+int lshrs_cosine_ragged_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                            const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
+                            float* scores, int32_t* err, void* stream) {
+  return cosine_ragged<F16>(corpus, m, ldc, dim, queries, q, cand_rows, row_off, row_cnt, total, scores, err, stream);
 }
 
 int lshrs_l2_normalize_f32(const float* X, int64_t n, int64_t ldx, int32_t dim, float* out, uint8_t* status,

@@ -5,6 +5,9 @@ Function names, argument meaning, return types and error behaviour follow
 lshrs/utils/similarity.py:26-183 and lshrs/utils/norm.py:4-61; the arithmetic runs in
 ``cosine_kernel`` / ``topk_kernel`` of ``csrc/rerank.hip`` (C ABI:
 ``lshrs_cosine_batch_f32`` / ``lshrs_topk_desc_f32``).  No CPU compute path.
+A device-resident corpus may also hold bfloat16 or float16 rows (``corpus_entry``: the one place that
+knows which); they are converted to float32 exactly inside the kernel, so the scores are those of the
+upcast corpus, and the queries stay float32.
 
 Numerics: the kernel evaluates ``dot(c, q) / (||c|| * ||q||)`` in float32 with a fixed
 per-lane + wave-tree summation order; the reference normalises first and then takes the
@@ -40,21 +43,45 @@ def _as_matrix(candidates, dim: Optional[int] = None) -> np.ndarray:
     return np.ascontiguousarray(np.stack(rows))
 
 
+class CorpusError(TypeError, ValueError):
+    """A corpus the rerank cannot read as it is (a TypeError for the device-level entry, a ValueError for ``LSHRS``)."""
+
+
+# element type of a device corpus -> suffix of the C entries that read it (include/lshrs_hip.h): 16-bit elements are converted
+# to f32 exactly, so a bfloat16 / float16 corpus scores as its upcast would, at half the bytes gathered
+_CORPUS_ENTRY = {"float32": "f32", "bfloat16": "bf16", "float16": "f16"}
+
+
+def corpus_entry(corpus, form: str, dim: Optional[int] = None) -> str:
+    """The one place that decides which corpora the rerank reads on the device: a CUDA tensor of float32, bfloat16 or float16,
+    shape ``(m, dim)`` with a unit inner stride (any row stride).  Returns the name of the C entry of ``form`` ("batch" or
+    "ragged") that scores against it; raises :class:`CorpusError` naming what is accepted otherwise."""
+    torch = _native.require_gpu()
+    suffix = _CORPUS_ENTRY.get(str(corpus.dtype).replace("torch.", "")) if isinstance(corpus, torch.Tensor) else None
+    if (suffix is None or not corpus.is_cuda or corpus.dim() != 2 or corpus.stride(1) != 1
+            or (dim is not None and int(corpus.shape[1]) != dim)):
+        want = "(m, dim)" if dim is None else f"(m, {dim})"
+        raise CorpusError(f"corpus must be a float32, bfloat16 or float16 device tensor of shape {want} with unit inner "
+                          f"stride; got {getattr(corpus, 'dtype', type(corpus).__name__)} {tuple(getattr(corpus, 'shape', ()))}")
+    return f"lshrs_cosine_{form}_{suffix}"
+
+
 def cosine_scores_device(corpus, queries, cand_idx=None, *, c: Optional[int] = None):
     """Device-level entry: tensors in, tensors out.
 
-    corpus (m, dim) f32, queries (q, dim) f32, cand_idx (q, c) int64 or None (then the candidates
-    of query i are corpus rows [i*c, (i+1)*c)).  Returns (scores (q, c) f32, status (q, c) u8,
-    qstatus (q,) u8) on the same device; see include/lshrs_hip.h for the status codes.
+    corpus (m, dim) float32, bfloat16 or float16 (16-bit elements are converted to f32 exactly), queries (q, dim) f32,
+    cand_idx (q, c) int64 or None (then the candidates of query i are corpus rows [i*c, (i+1)*c)).  Returns
+    (scores (q, c) f32, status (q, c) u8, qstatus (q,) u8) on the same device; see include/lshrs_hip.h for the status codes.
     """
     torch = _native.require_gpu()
     lib = _native.load()
-    if corpus.dtype != torch.float32 or queries.dtype != torch.float32:
-        raise TypeError("corpus and queries must be float32 tensors")
+    if queries.dtype != torch.float32:
+        raise TypeError("queries must be a float32 tensor")
     if corpus.dim() != 2 or queries.dim() != 2 or corpus.shape[1] != queries.shape[1]:
         raise ValueError("corpus must be (m, dim) and queries (q, dim)")
     if corpus.stride(1) != 1:
         corpus = corpus.contiguous()
+    entry = corpus_entry(corpus, "batch")
     queries = queries.contiguous()
     dev = corpus.device
     q = int(queries.shape[0])
@@ -73,10 +100,10 @@ def cosine_scores_device(corpus, queries, cand_idx=None, *, c: Optional[int] = N
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
         _native.check(
-            lib.lshrs_cosine_batch_f32(corpus.data_ptr(), corpus.shape[0], corpus.stride(0), corpus.shape[1],
-                                       queries.data_ptr(), q, cand_idx.data_ptr() if cand_idx is not None else None,
-                                       c, scores.data_ptr(), status.data_ptr(), qstatus.data_ptr(), stream),
-            "lshrs_cosine_batch_f32")
+            getattr(lib, entry)(corpus.data_ptr(), corpus.shape[0], corpus.stride(0), corpus.shape[1],
+                                queries.data_ptr(), q, cand_idx.data_ptr() if cand_idx is not None else None,
+                                c, scores.data_ptr(), status.data_ptr(), qstatus.data_ptr(), stream),
+            entry)
     return scores, status, qstatus
 
 
