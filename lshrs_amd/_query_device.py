@@ -9,7 +9,8 @@ download (ids, scores, bounds):
   ``lshrs_query_collide_*`` (sort / count / order inside a workgroup's LDS) -> [``lshrs_cosine_ragged_{f32,bf16,f16}`` on the
   resident corpus] -> ``lshrs_query_rank_f32`` (order by score, cut to top-p / top-k, compact)
 
-``DeviceBuckets`` mirrors the array segments of a store (``InMemoryStorage.array_segments``) in device memory: uploaded
+``DeviceBuckets`` mirrors the array segments of a store (``InMemoryStorage.array_segments_snapshot``, asked through
+``LSHRS._bucket_table``, which keeps the table beside the snapshot's token) in device memory: uploaded
 the first time a query meets them, kept until the store replaces them.  Stores that only answer ``get_bucket`` (the
 reference's ``RedisStorage``) hand their (query, member, band) pairs over flat (``collide_pairs``).  No CPU compute path:
 the host only moves arrays.
@@ -23,6 +24,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _native
+from .similarity import _upload as upload
 from .similarity import corpus_entry
 from .windows import _U
 
@@ -34,14 +36,29 @@ class TooLarge(Exception):
     layout: the caller counts this batch on the host."""
 
 
-def upload(torch, a: np.ndarray, dev):
-    """Host array -> tensor on ``dev`` (the array is only read: a read-only view goes up without a defensive copy)."""
-    import warnings
+def queries_on(arr, dev):
+    """Query rows - a host array (a stride-0 ``v[None]`` included) or a tensor on any device - as a float32 tensor on ``dev``
+    with a unit inner stride and rows that do not overlap (the kernels take a row stride)."""
+    torch = _native.require_gpu()
+    if not isinstance(arr, torch.Tensor):
+        if arr.strides[0] < arr.shape[1] * 4:           # (`v[None]`: NumPy gives the new axis stride 0)
+            arr = arr.reshape(-1).copy().reshape(arr.shape)
+        return upload(torch, arr, dev)
+    x = arr.to(dev) if arr.device != dev else arr
+    return x if x.stride(1) == 1 and x.stride(0) >= x.shape[1] else x.contiguous()
 
-    a = np.ascontiguousarray(a)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", UserWarning)
-        return torch.from_numpy(a).to(dev)
+
+def corpus_on(corpus, dev, dim: int):
+    """The corpus of a rerank - array-like or tensor - as a tensor on a GPU (``dev`` unless it lives on one already) that
+    ``corpus_entry`` accepts; another dtype or shape raises its ``ValueError``."""
+    torch = _native.require_gpu()
+    table = corpus if isinstance(corpus, torch.Tensor) else upload(torch, np.asarray(corpus, dtype=np.float32), dev)
+    if not table.is_cuda:
+        table = table.to(dev)
+    if table.dim() == 2 and table.stride(1) != 1:
+        table = table.contiguous()
+    corpus_entry(table, "ragged", dim)
+    return table
 
 
 def _bbits(num_bands: int) -> int:

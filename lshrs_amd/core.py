@@ -24,7 +24,6 @@ from __future__ import annotations
 import itertools
 import json
 import logging
-import math
 import warnings
 from pathlib import Path
 from threading import Lock
@@ -33,6 +32,7 @@ from typing import Any, Callable, Dict, Iterable, Iterator, List, Optional, Sequ
 import numpy as np
 
 from . import _hostblas
+from . import _query_host as qh
 from ._gcpause import gc_paused as _gc_paused
 from .bandrows import get_optimal_config
 from .hasher import LSHHasher
@@ -110,22 +110,6 @@ class _DeferredStorage:
         if item in ("batch_add_csr", "batch_add_packed", "get_buckets_many") and self._real is None:
             raise AttributeError(item)          # (capability probes must not open a connection)
         return getattr(self._resolve(), item)
-
-
-def _ragged_positions(starts: np.ndarray, lens: np.ndarray) -> np.ndarray:
-    """Concatenation of ``arange(starts[i], starts[i] + lens[i])`` over i."""
-    total = int(lens.sum())
-    return np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens) + np.repeat(starts, lens)
-
-
-def _split_rows(flat: list, lens: np.ndarray) -> List[list]:
-    """A flat Python list cut into consecutive pieces of the given lengths."""
-    ends = np.cumsum(lens).tolist()
-    out, lo = [], 0
-    for hi in ends:
-        out.append(flat[lo:hi])
-        lo = hi
-    return out
 
 
 class LSHRS:
@@ -210,7 +194,7 @@ class LSHRS:
 
         self._dev_buckets = DeviceBuckets()  # device mirror of the store's bucket arrays (query_many)
         self._one_query: Dict[int, Any] = {}    # per device: the pinned / device buffers of the single-query chain
-        self._one_table = None          # (store token, band bytes, device) -> the segments' descriptor on the device (_query_one_device)
+        self._one_table = None          # the store's segments as a device table, beside the token of their snapshot (_bucket_table)
         self._config: Dict[str, Any] = {
             "dim": dim, "num_perm": num_perm, "num_bands": num_bands, "rows_per_band": rows_per_band,
             "similarity_threshold": similarity_threshold, "buffer_size": buffer_size, "seed": seed,
@@ -290,48 +274,29 @@ class LSHRS:
             return
         if vectors is None:
             vectors = self._require_vector_fetch_fn()(indices)
-        resident = _device_tensor(vectors)
-        if resident is not None:
-            # vectors that already live on a GPU (round 6): hashed where they are, their buckets grouped on the device - only the
-            # bucket arrays cross the link (a store that takes arrays; any other store gets the host form of the same rows)
-            id_arr, resident = self._check_batch(indices, resident)
-            if self._streams_buckets(int(resident.shape[0]) * self._config["num_bands"]):
-                self.flush()
-                with self._open_ingest(inline=True) as ingest:
-                    ingest.submit(id_arr, resident)
-                return
-            vectors = resident.detach().cpu().numpy()
-        arr = np.asarray(vectors, dtype=np.float32)
-        if arr.ndim != 2 or arr.shape[1] != self._dim:
-            raise ValueError(f"Vectors must have shape (n, {self._dim}); received {arr.shape}")
-        if arr.shape[0] != len(indices):
-            raise ValueError(
-                "Number of vectors does not match number of indices "
-                f"(received {arr.shape[0]} vectors for {len(indices)} indices)")
-
-        if self._streams_buckets(arr.shape[0] * self._config["num_bands"]):
+        arr = self._check_rows(indices, vectors)
+        n_ops = int(arr.shape[0]) * self._config["num_bands"]
+        resident = _device_tensor(arr) is not None
+        if self._streams_buckets(n_ops):
             # array path, pipelined (lshrs_amd/_ingest.py): copy + signature pass chunk by chunk, every chunk's
             # keys grouped into buckets on the device under the next chunk's copy, bucket arrays to the storage in row order.
-            # Anything already buffered goes first so the storage sees operations in the original order.
+            # Anything already buffered goes first so the storage sees operations in the original order.  Vectors that already
+            # live on a GPU (round 6) are hashed where they are: only the bucket arrays cross the link.
             self.flush()
-            id_arr, arr = self._check_batch(indices, arr)
-            lanes = self._ingest_hashers()
+            id_arr, arr = self._id_array(indices), (arr if resident else np.ascontiguousarray(arr))
             with self._open_ingest(inline=True) as ingest:
-                if len(lanes) == 1 or arr.shape[0] < 2 * self.lane_rows:
+                if resident or len(self._ingest_hashers()) == 1 or arr.shape[0] < 2 * self.lane_rows:
                     ingest.submit(id_arr, arr)
                 else:                       # several devices: contiguous slices of whole chunks, dealt round-robin
                     for lo in range(0, arr.shape[0], self.lane_rows):
                         ingest.submit(id_arr[lo:lo + self.lane_rows], arr[lo:lo + self.lane_rows])
             return
-        sink = self._packed_sink(arr.shape[0] * self._config["num_bands"])
+        if resident:                        # (a store that does not take arrays gets the host form of the same rows)
+            arr = np.asarray(arr.detach().cpu().numpy(), dtype=np.float32)
+        sink = self._packed_sink(n_ops)
         packed = sink is not None
-        if packed:
-            id_arr = np.asarray(indices)
-            id_arr = id_arr.astype(np.int64) if id_arr.dtype.kind in "iuf" else np.array([int(i) for i in indices], dtype=np.int64)
-            ids = id_arr
-        else:
-            ids = [int(i) for i in indices]
-            id_arr = None
+        id_arr = self._id_array(indices) if packed else None
+        ids = id_arr if packed else [int(i) for i in indices]
         keys, flags = self._hasher.hash_batch_packed(arr, return_row_flags=True)
 
         # first row the per-vector loop of the reference would have choked on, and why
@@ -431,14 +396,10 @@ class LSHRS:
             return []
 
         if top_p is None:
-            if top_k is None:
-                top_k = len(candidate_indices)
-            if top_k <= 0:
-                raise ValueError("top_k must be greater than zero when provided")
+            qh.check_cut(top_k, None)
             return candidate_indices[:top_k]
 
-        if not 0 < top_p <= 1:
-            raise ValueError("top_p must be within the range (0, 1]")
+        qh.check_cut(None, top_p)
         if self._corpus is not None:
             # the indexed vectors are resident on the device (set_corpus): gathered and scored there, nothing fetched
             from .similarity import rerank_batch
@@ -446,15 +407,11 @@ class LSHRS:
             ranked = rerank_batch(query_vector[None], self._corpus, np.asarray([candidate_indices], dtype=np.int64),
                                   k=len(candidate_indices))[0]
         else:
-            arr = self._fetch_checked(self._require_vector_fetch_fn(), candidate_indices)
+            arr = qh.fetch_checked(self._require_vector_fetch_fn(), self._dim, candidate_indices)
             ranked = top_k_cosine(query_vector, arr, k=len(candidate_indices))
         scored = [(candidate_indices[pos], score) for pos, score in ranked]
-        limit = max(1, math.ceil(len(scored) * top_p))
-        if top_k is not None:
-            if top_k <= 0:
-                raise ValueError("top_k must be greater than zero when provided")
-            limit = min(limit, top_k)
-        return scored[:limit]
+        qh.check_cut(top_k, top_p)                  # (the reference looks at `top_k` behind the rerank: main.py:653)
+        return scored[:int(qh.keep_counts(len(scored), top_k, top_p))]
 
     def _query_one_device(self, query_vector: np.ndarray, top_k, top_p):
         """:meth:`query` as ONE chain of launches with one wait at its end (``_query_device.OneQuery``: signature kernel, bucket
@@ -478,53 +435,29 @@ class LSHRS:
                 corpus_entry(corpus, "ragged", self._dim)       # a device corpus the rerank reads as it is (float32 / bf16 / f16)
             except ValueError:
                 return None
-        st = self._storage
-        if isinstance(st, _DeferredStorage):
-            st = st._resolve()
         dev = corpus.device if rerank else h._torch_device()
-        # what the store's segments look like on the device: kept beside the store's change token (one comparison per call
-        # instead of a walk over the segments under the store's lock)
-        token_fn = getattr(st, "array_segments_token", None)
-        token = token_fn() if callable(token_fn) else None
-        kept = self._one_table
-        if token is not None and kept is not None and kept[0] == (id(st), token, h.band_bytes, dev.index):
-            desc, nseg, max_id = kept[1]
-        else:
-            segs = st.array_segments(h.band_bytes) if callable(getattr(st, "array_segments", None)) else None
-            if segs is None:
-                return None
-            try:
-                desc, nseg, max_id = self._dev_buckets.table(segs, dev)
-            except qd.TooLarge:
-                return None
-            token = token_fn() if callable(token_fn) else None        # (array_segments may have folded the segments)
-            # (with it: the segments and the mirror's device arrays the descriptor points into - alive as long as the entry is)
-            self._one_table = None if token is None else ((id(st), token, h.band_bytes, dev.index), (desc, nseg, max_id), segs,
-                                                          self._dev_buckets._table, st)      # (and the store: its id is the key)
-        one = self._one_query.get(dev.index)
-        if one is None or one.shape != (h.num_bands, h.band_bytes, h.dim):
-            one = self._one_query[dev.index] = qd.OneQuery(h, dev)
         try:
+            table = self._bucket_table(dev, h.band_bytes)
+            if table is None:
+                return None
+            one = self._one_query.get(dev.index)
+            if one is None or one.shape != (h.num_bands, h.band_bytes, h.dim):
+                one = self._one_query[dev.index] = qd.OneQuery(h, dev)
             k_arg = top_k if (top_k is not None and top_k > 0) else -1
-            ucount, ids, scores, flag = one.run(h, query_vector, desc, nseg, max_id, k_arg, float(top_p) if rerank else -1.0, corpus)
+            ucount, ids, scores, flag = one.run(h, query_vector, *table, k_arg, float(top_p) if rerank else -1.0, corpus)
+            if flag & 1:
+                raise ValueError(_ZERO_MSG)
+            if ucount < 0:
+                # more pairs than the chain's fixed capacity: the batch form, which sizes its arrays by what it finds (and takes
+                # lists beyond the LDS network through global memory)
+                ids, scores, _ = self._query_many_device(query_vector[None], top_k if (top_k is None or top_k > 0) else None,
+                                                         top_p if rerank else None, corpus if rerank else None)
+                ucount = len(ids)
         except qd.TooLarge:
             return None
-        if flag & 1:
-            raise ValueError(_ZERO_MSG)
-        if ucount < 0:                       # more pairs than the chain's fixed capacity: the batch form, which sizes its arrays
-            try:                             # by what it finds (and takes lists beyond the LDS network through global memory)
-                got = self._query_many_device(query_vector[None], top_k if (top_k is None or top_k > 0) else None,
-                                              top_p if rerank else None, corpus if rerank else None)
-            except qd.TooLarge:
-                return None
-            ids, scores = got[0], got[1]
-            ucount = 1 if len(ids) else 0
         if ucount == 0:
             return []
-        if bad_p:
-            raise ValueError("top_p must be within the range (0, 1]")
-        if top_k is not None and top_k <= 0:
-            raise ValueError("top_k must be greater than zero when provided")
+        qh.check_cut(top_k, top_p)
         if scores is None:
             return ids.tolist()
         return list(zip(ids.tolist(), scores.astype(np.float64).tolist()))
@@ -566,30 +499,17 @@ class LSHRS:
         kernels' 16 384 entries is counted on the host), "device" (raise instead), "host" (NumPy counting between the two
         launches: round 5's path)."""
         resident = _device_tensor(vectors)         # queries that already live on a GPU stay there (no copy over the link, no host array)
+        arr = resident if resident is not None else np.asarray(vectors, dtype=np.float32)
+        if len(arr.shape) != 2 or int(arr.shape[1]) != self._dim:
+            raise ValueError(f"Vectors must have shape (n, {self._dim}); received {tuple(arr.shape)}")
         if resident is not None:
-            if resident.dim() != 2 or int(resident.shape[1]) != self._dim:
-                raise ValueError(f"Vectors must have shape (n, {self._dim}); received {tuple(resident.shape)}")
-            if resident.dtype != __import__("torch").float32:
-                resident = resident.float()
-            arr = None
-            shape0 = int(resident.shape[0])
-        else:
-            arr = np.asarray(vectors, dtype=np.float32)
-            if arr.ndim != 2 or arr.shape[1] != self._dim:
-                raise ValueError(f"Vectors must have shape (n, {self._dim}); received {arr.shape}")
-            shape0 = arr.shape[0]
-        if top_p is None and top_k is not None and top_k <= 0:
-            raise ValueError("top_k must be greater than zero when provided")
-        if top_p is not None and not 0 < top_p <= 1:
-            raise ValueError("top_p must be within the range (0, 1]")
-        if top_p is not None and top_k is not None and top_k <= 0:
-            raise ValueError("top_k must be greater than zero when provided")
+            arr = resident.float()                  # (itself where it is float32 already)
+        qh.check_cut(top_k, top_p)
         if engine not in ("auto", "device", "host"):
             raise ValueError("engine must be 'auto', 'device' or 'host'")
         if corpus is None:
             corpus = self._corpus
-        nq = shape0
-        if nq == 0:
+        if int(arr.shape[0]) == 0:
             empty = (np.empty(0, np.int64), None if top_p is None else np.empty(0, np.float32), np.zeros(1, np.int64))
             return empty if return_arrays else []
         on_device = (engine != "host" and callable(getattr(self._hasher, "hash_device", None))
@@ -601,44 +521,36 @@ class LSHRS:
             from ._query_device import TooLarge
 
             try:
-                got = self._query_many_device(arr if resident is None else resident, top_k, top_p, corpus)
+                got = self._query_many_device(arr, top_k, top_p, corpus)
             except TooLarge:
                 if engine == "device":
                     raise
         if got is None:
-            got = self._query_many_host(arr if resident is None else resident.cpu().numpy(), top_k, top_p, corpus)
+            got = self._query_many_host(arr if resident is None else arr.cpu().numpy(), top_k, top_p, corpus)
         ids, scores, bounds = got
         if return_arrays:
             return ids, scores, bounds
         keep = np.diff(bounds)
         with _gc_paused():
             if scores is None:
-                return _split_rows(ids.tolist(), keep)
-            return _split_rows(list(zip(ids.tolist(), scores.astype(np.float64).tolist())), keep)
+                return qh.split_rows(ids.tolist(), keep)
+            return qh.split_rows(list(zip(ids.tolist(), scores.astype(np.float64).tolist())), keep)
 
-    def _query_many_device(self, arr: np.ndarray, top_k, top_p, corpus):
+    def _query_many_device(self, arr, top_k, top_p, corpus):
         """``query_many`` with everything between the upload of the queries and the download of the answers on the device."""
         from . import _native
         from . import _query_device as qd
 
         torch = _native.require_gpu()
         nq = int(arr.shape[0])
-        resident = isinstance(arr, torch.Tensor)
-        if not resident and arr.strides[0] < arr.shape[1] * 4:            # (`v[None]`: NumPy gives the new axis stride 0 - the kernels take a row stride)
-            arr = arr.reshape(-1).copy().reshape(nq, arr.shape[1])
-        if corpus is not None and isinstance(corpus, torch.Tensor) and corpus.is_cuda:
+        if _device_tensor(corpus) is not None:
             dev = corpus.device
-        elif resident:
+        elif isinstance(arr, torch.Tensor):
             dev = arr.device
         else:
             dev = self._hasher._torch_device()
         with torch.cuda.device(dev):
-            if resident:                                # queries handed over on a GPU: rows of `dim` floats, on the device that ranks them
-                x = arr.to(dev) if arr.device != dev else arr
-                if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
-                    x = x.contiguous()
-            else:
-                x = qd.upload(torch, arr, dev)
+            x = qd.queries_on(arr, dev)
             flags = torch.empty(nq, dtype=torch.uint8, device=dev)
             keys_dev = self._hasher.hash_device(x, row_flags=flags)
             if bool((flags & 1).any()):
@@ -652,63 +564,51 @@ class LSHRS:
             if lists.total == 0:
                 return np.empty(0, np.int64), np.empty(0, np.float32), np.zeros(nq + 1, np.int64)
             if corpus is not None:
-                table = corpus if isinstance(corpus, torch.Tensor) else qd.upload(torch, np.asarray(corpus, dtype=np.float32), dev)
-                if not table.is_cuda:
-                    table = table.to(dev)
-                if table.dim() == 2 and table.stride(1) != 1:
-                    table = table.contiguous()
-                corpus_entry(table, "ragged", self._dim)            # (raises a ValueError naming the dtypes it takes)
-                return qd.rank_and_cut(lists, top_k, top_p, queries_dev=x, corpus=table)
+                return qd.rank_and_cut(lists, top_k, top_p, queries_dev=x, corpus=qd.corpus_on(corpus, dev, self._dim))
             # no resident corpus: the candidates' vectors come from the caller's fetch function, list by list as the reference
-            # asks for them (main.py:629), and travel to the device as one table
-            fetch = self._require_vector_fetch_fn()
-            pair_off, ucount = lists.pair_off.cpu().numpy(), lists.ucount.cpu().numpy()
-            cand = lists.cand_ids.cpu().numpy()
-            rows_host = np.zeros(max(1, lists.total), dtype=np.int64)
-            blocks, pos = [], 0
-            for qi in np.flatnonzero(ucount):
-                lo, u = int(pair_off[qi]), int(ucount[qi])
-                blocks.append(self._fetch_checked(fetch, cand[lo:lo + u].tolist()))
-                rows_host[lo:lo + u] = np.arange(pos, pos + u, dtype=np.int64)
-                pos += u
-            table = qd.upload(torch, np.concatenate(blocks, axis=0), dev)
-            return qd.rank_and_cut(lists, top_k, top_p, queries_dev=x, corpus=table, cand_rows=qd.upload(torch, rows_host, dev))
+            # asks for them (main.py:629), and travel to the device as one table; candidate j reads row `rows[j]` of it
+            ucount = lists.ucount.cpu().numpy()
+            at = qh.ragged_positions(lists.pair_off.cpu().numpy()[:nq], ucount)      # where the lists sit in `cand_ids`
+            table = qh.fetch_table(self._require_vector_fetch_fn(), self._dim, lists.cand_ids.cpu().numpy()[at],
+                                   np.r_[0, np.cumsum(ucount)])
+            rows = np.zeros(max(1, lists.total), dtype=np.int64)
+            rows[at] = np.arange(at.shape[0], dtype=np.int64)
+            return qd.rank_and_cut(lists, top_k, top_p, queries_dev=x, corpus=qd.upload(torch, table, dev),
+                                   cand_rows=qd.upload(torch, rows, dev))
 
     def _device_lists(self, qd, keys_dev, dev):
         """Every query's candidates, counted and ordered on the device: from the device mirror of the store's bucket arrays
         where the store keeps arrays, else from one ``get_bucket`` per (query, band) (the reference's storage interface,
         lshrs/storage/redis.py:282) with the pairs handed over flat."""
-        st = self._storage
-        if isinstance(st, _DeferredStorage):
-            st = st._resolve()
         nq, nb, bb = (int(v) for v in keys_dev.shape)
-        segs = st.array_segments(bb) if callable(getattr(st, "array_segments", None)) else None
-        if segs is not None:
-            desc, nseg, max_id = self._dev_buckets.table(segs, dev)
-            return qd.candidates_from_index(keys_dev, desc, nseg, max_id)
-        keys = keys_dev.cpu().numpy()
-        ms, bs, off = [], [], np.zeros(nq + 1, dtype=np.int64)
-        for qi in range(nq):
-            n = 0
-            for b in range(nb):
-                mem = st.get_bucket(b, keys[qi, b].tobytes())
-                if mem:
-                    ms.append(np.fromiter((int(v) for v in mem), dtype=np.int64, count=len(mem)))
-                    bs.append(np.full(len(mem), b, dtype=np.int32))
-                    n += len(mem)
-            off[qi + 1] = off[qi] + n
-        members = np.concatenate(ms) if ms else np.empty(0, np.int64)
-        bands = np.concatenate(bs) if bs else np.empty(0, np.int32)
-        return qd.candidates_from_pairs(members, bands, off, nb, dev)
+        table = self._bucket_table(dev, bb)
+        if table is not None:
+            return qd.candidates_from_index(keys_dev, *table)
+        q, bands, members = qh.bucket_pairs(self._resolved_storage(), keys_dev.cpu().numpy())
+        return qd.candidates_from_pairs(members, bands, np.searchsorted(q, np.arange(nq + 1)).astype(np.int64), nb, dev)
 
-    def _fetch_checked(self, fetch, ids: list) -> np.ndarray:
-        got = np.asarray(fetch(ids), dtype=np.float32)
-        if got.ndim != 2 or got.shape[1] != self._dim:
-            raise ValueError(f"Fetched vectors must have shape (n, {self._dim}); received {got.shape}")
-        if got.shape[0] != len(ids):
-            raise ValueError("vector_fetch_fn returned mismatched batch size "
-                             f"(expected {len(ids)}, received {got.shape[0]})")
-        return got
+    def _bucket_table(self, dev, band_bytes: int):
+        """``DeviceBuckets.table`` of the store's bucket arrays on ``dev``, or None where the store does not keep every bucket
+        of this key width as arrays (the caller reads it through ``get_bucket``).  Kept beside the token that came back WITH the
+        segments (``array_segments_snapshot``: one acquisition of the store's lock): while the store does not change a call
+        costs one token comparison, and an ``index()`` that lands behind the snapshot is seen by the next call.  A store that
+        only has ``array_segments`` is asked every time."""
+        st = self._resolved_storage()
+        token_fn = getattr(st, "array_segments_token", None)
+        kept = self._one_table
+        if kept is not None and callable(token_fn) and kept[0] == (id(st), token_fn(), band_bytes, dev.index):
+            return kept[1]
+        if callable(getattr(st, "array_segments_snapshot", None)):
+            segs, token = st.array_segments_snapshot(band_bytes)
+        else:                                       # (a store of another kind: nothing to keep the answer beside)
+            segs, token = (st.array_segments(band_bytes) if callable(getattr(st, "array_segments", None)) else None), None
+        if segs is None:
+            return None
+        table = self._dev_buckets.table(segs, dev)
+        # (with it what the descriptor points into - the segments, the mirror's device arrays - and the store, whose id is the key)
+        self._one_table = None if token is None else ((id(st), token, band_bytes, dev.index), table, segs,
+                                                        self._dev_buckets._table, st)
+        return table
 
     def _query_many_host(self, arr: np.ndarray, top_k, top_p, corpus):
         """``query_many`` with the collision counting in NumPy between the signature launch and the rerank launch (round 5;
@@ -720,8 +620,8 @@ class LSHRS:
         um, bounds = self._ordered_candidates_arrays(keys)
         lens = np.diff(bounds)
         if top_p is None:
-            keep = lens if top_k is None else np.minimum(lens, top_k)
-            return um[_ragged_positions(bounds[:-1], keep)], None, np.r_[0, np.cumsum(keep)].astype(np.int64)
+            keep = qh.keep_counts(lens, top_k, None)
+            return um[qh.ragged_positions(bounds[:-1], keep)], None, np.r_[0, np.cumsum(keep)].astype(np.int64)
 
         # rerank every non-empty candidate list in one launch: a (q, c_max) index matrix padded with -1
         # (out-of-range entries score NaN, which the device sort places last)
@@ -733,18 +633,13 @@ class LSHRS:
         cand_ids = np.full((nq, c_max), -1, dtype=np.int64)
         cand_ids[rows, cols] = um
         if corpus is None:
-            fetch = self._require_vector_fetch_fn()
-            blocks = [self._fetch_checked(fetch, um[bounds[qi]:bounds[qi + 1]].tolist()) for qi in np.flatnonzero(lens)]
-            table = np.concatenate(blocks, axis=0)
+            table = qh.fetch_table(self._require_vector_fetch_fn(), self._dim, um, bounds)
             cand = np.full((nq, c_max), -1, dtype=np.int64)
             cand[rows, cols] = np.arange(um.shape[0], dtype=np.int64)     # row of `table` = position in the flat list
         else:
             table, cand = corpus, cand_ids
         order, scores = _rerank_padded(arr, table, cand)                   # (q, c_max): positions, descending scores
-        keep = np.maximum(1, np.ceil(lens * top_p).astype(np.int64))       # (reference: main.py:652-657)
-        keep[lens == 0] = 0
-        if top_k is not None:
-            keep = np.minimum(keep, top_k)
+        keep = qh.keep_counts(lens, top_k, top_p)
         krows = np.repeat(np.arange(nq, dtype=np.int64), keep)
         kcols = np.arange(int(keep.sum()), dtype=np.int64) - np.repeat(np.cumsum(keep) - keep, keep)
         return (cand_ids[krows, order[krows, kcols]], np.ascontiguousarray(scores[krows, kcols], dtype=np.float32),
@@ -909,52 +804,16 @@ class LSHRS:
         return counts
 
     def _ordered_candidates_arrays(self, keys: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-        """For every query: the stored ids that share at least one band bucket with it, ordered by (-collisions, id) -
-        ``_candidate_counts`` + the sort of ``query`` (lshrs/core/main.py:1088-1111, :614) for a whole batch, as array
-        work: bucket members are gathered as flat (query, member) pairs, one sort counts the collisions, one orders the
-        candidates.  Returns ``(ids, bounds)``: query ``i``'s candidates are ``ids[bounds[i]:bounds[i + 1]]``.  No Python
-        object per member."""
-        nq, nb = keys.shape[0], keys.shape[1]
+        """``_query_host.order_candidates`` of these band keys' buckets (one vectorised lookup where the store has one)."""
         if hasattr(self._storage, "get_buckets_many"):
             q, m = self._storage.get_buckets_many(keys)
-        else:   # the reference's storage interface: one bucket read per (query, band), members concatenated
-            qs, ms = [], []
-            for qi in range(nq):
-                for band_id in range(nb):
-                    mem = self._storage.get_bucket(band_id, keys[qi, band_id].tobytes())
-                    if mem:
-                        ms.append(np.fromiter((int(v) for v in mem), dtype=np.int64, count=len(mem)))
-                        qs.append(np.full(len(mem), qi, dtype=np.int64))
-            q = np.concatenate(qs) if qs else np.empty(0, np.int64)
-            m = np.concatenate(ms) if ms else np.empty(0, np.int64)
-        if q.size == 0:
-            return np.empty(0, np.int64), np.zeros(nq + 1, dtype=np.int64)
-        qbits, cbits = max(1, int(nq - 1).bit_length()), int(nb).bit_length()
-        mbits = 63 - qbits - cbits
-        if int(m.min()) >= 0 and int(m.max()) < (1 << mbits):
-            # one 64-bit key per pair: (query, member), then (query, bands - collisions, member): two plain sorts
-            pair = np.sort((q << mbits) | m)
-            first = np.r_[True, pair[1:] != pair[:-1]]
-            starts = np.flatnonzero(first)
-            counts = np.diff(np.r_[starts, pair.shape[0]])     # (one pair per (query, band, member): the lookup's contract)
-            uniq = pair[starts]
-            uq, um = uniq >> mbits, uniq & ((1 << mbits) - 1)
-            ranked = np.sort((uq << (mbits + cbits)) | ((nb - counts) << mbits) | um)
-            uq, um = ranked >> (mbits + cbits), ranked & ((1 << mbits) - 1)
         else:
-            order = np.lexsort((m, q))                           # by query, then member
-            q, m = q[order], m[order]
-            first = np.r_[True, (q[1:] != q[:-1]) | (m[1:] != m[:-1])]
-            starts = np.flatnonzero(first)
-            counts = np.diff(np.r_[starts, q.shape[0]])
-            uq, um = q[starts], m[starts]
-            rank = np.lexsort((um, -counts, uq))                 # by query, then -collisions, then id
-            uq, um = uq[rank], um[rank]
-        return um, np.searchsorted(uq, np.arange(nq + 1)).astype(np.int64)
+            q, _, m = qh.bucket_pairs(self._storage, keys)
+        return qh.order_candidates(q, m, keys.shape[0], keys.shape[1])
 
     def _ordered_candidates_many(self, keys: np.ndarray) -> List[List[int]]:
         um, bounds = self._ordered_candidates_arrays(keys)
-        return _split_rows(um.tolist(), np.diff(bounds))
+        return qh.split_rows(um.tolist(), np.diff(bounds))
 
     lane_rows = 262_144      # rows per unit when ONE index() call is cut up for several devices (two stream chunks)
 
@@ -977,9 +836,9 @@ class LSHRS:
         return CsrIngest(self._ingest_hashers(), self._packed_sink(1 << 62), lambda: ValueError(_ZERO_MSG),
                          lambda: ValueError("index must be non-negative"), inline=inline)
 
-    def _check_batch(self, indices, vectors):
-        """(ids int64, rows float32 C-contiguous) of one batch, with the reference's shape errors (main.py:504-511); rows that
-        live on a GPU (a torch tensor) stay where they are."""
+    def _check_rows(self, indices, vectors):
+        """The rows of one batch - float32; a torch tensor that lives on a GPU stays where it is - with the reference's shape
+        errors (main.py:504-511)."""
         resident = _device_tensor(vectors)
         arr = resident if resident is not None else np.asarray(vectors, dtype=np.float32)
         shape = tuple(int(v) for v in arr.shape)
@@ -989,9 +848,21 @@ class LSHRS:
             raise ValueError(
                 "Number of vectors does not match number of indices "
                 f"(received {shape[0]} vectors for {len(indices)} indices)")
+        return arr
+
+    @staticmethod
+    def _id_array(indices) -> np.ndarray:
         id_arr = np.asarray(indices)
-        id_arr = id_arr.astype(np.int64) if id_arr.dtype.kind in "iuf" else np.array([int(i) for i in indices], dtype=np.int64)
-        return id_arr, (arr if resident is not None else np.ascontiguousarray(arr))
+        return id_arr.astype(np.int64) if id_arr.dtype.kind in "iuf" else np.array([int(i) for i in indices], dtype=np.int64)
+
+    def _check_batch(self, indices, vectors):
+        """(ids int64, rows float32 C-contiguous) of one batch; rows that live on a GPU stay where they are."""
+        arr = self._check_rows(indices, vectors)
+        return self._id_array(indices), (arr if _device_tensor(arr) is not None else np.ascontiguousarray(arr))
+
+    def _resolved_storage(self):
+        st = self._storage
+        return st._resolve() if isinstance(st, _DeferredStorage) else st
 
     def _packed_sink(self, n_ops: int):
         """The object ``index()`` hands a batch's buckets to as arrays, or None for the reference's operation tuples
@@ -999,9 +870,7 @@ class LSHRS:
         mode = self._packed_ingest
         if mode is False or (mode == "auto" and n_ops < self.packed_auto_min_ops):
             return None
-        st = self._storage
-        if isinstance(st, _DeferredStorage):
-            st = st._resolve()                   # (index() is about to write to it anyway)
+        st = self._resolved_storage()            # (index() is about to write to it anyway)
         if hasattr(st, "batch_add_csr") or hasattr(st, "batch_add_packed"):
             return st
         if callable(getattr(st, "pipeline", None)) and callable(getattr(st, "bucket_key", None)):

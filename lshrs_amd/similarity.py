@@ -133,7 +133,10 @@ def topk_desc_device(scores, k: int):
     return order, sorted_scores
 
 
-def _raise_for_status(status, qstatus) -> None:
+def _raise_for_status(status, qstatus, valid=None) -> None:
+    """The reference's errors for what the cosine kernel reported; ``valid``: mask of the entries that count (padding does not)."""
+    if valid is not None:
+        status = status * valid
     if bool((qstatus != 0).any()) or bool((status == 1).any()):
         raise ValueError("Cannot normalize zero vector")
     if bool((status == 2).any()):
@@ -159,15 +162,22 @@ def l2_normalize_device(x):
     return out, status
 
 
-def _upload(torch, a: np.ndarray):
-    """Host array -> device tensor.  The array is only read: a read-only view (``np.frombuffer``, a memory map, a
-    broadcast) is uploaded as it is, without the copy ``torch.from_numpy`` asks for in its warning."""
+def _upload(torch, a: np.ndarray, dev="cuda"):
+    """Host array -> tensor on ``dev`` (default: the current GPU).  The array is only read: a read-only view (``np.frombuffer``,
+    a memory map, a broadcast) is uploaded as it is, without the copy ``torch.from_numpy`` asks for in its warning."""
     import warnings
 
     a = np.ascontiguousarray(a)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", UserWarning)
-        return torch.from_numpy(a).cuda()
+        return torch.from_numpy(a).to(dev)
+
+
+def _on_device(torch, a, dtype):
+    """``a`` - a tensor anywhere or array-like - as a tensor on the current GPU."""
+    if isinstance(a, torch.Tensor):
+        return a if a.is_cuda else a.cuda()
+    return _upload(torch, np.asarray(a, dtype=dtype))
 
 
 def l2_norm(vector) -> np.ndarray:
@@ -229,15 +239,9 @@ def rerank_batch(queries, corpus, cand_idx, *, k: int, return_tensors: bool = Fa
     if k <= 0:
         raise ValueError("k must be > 0")
     torch = _native.require_gpu()
-
-    def dev(a, dtype):
-        if isinstance(a, torch.Tensor):
-            return a.cuda() if not a.is_cuda else a
-        return _upload(torch, np.asarray(a, dtype=dtype))
-
-    d_q = dev(queries, np.float32)
-    d_c = dev(corpus, np.float32)
-    d_i = dev(cand_idx, np.int64)
+    d_q = _on_device(torch, queries, np.float32)
+    d_c = _on_device(torch, corpus, np.float32)
+    d_i = _on_device(torch, cand_idx, np.int64)
     scores, status, qstatus = cosine_scores_device(d_c, d_q, d_i)
     _raise_for_status(status, qstatus)
     order, sorted_scores = topk_desc_device(scores, min(k, int(d_i.shape[1])))
@@ -255,19 +259,11 @@ def rerank_padded_arrays(queries, corpus, cand_idx):
     device and sorts last, so row i is meaningful up to its number of valid candidates.  Zero-norm vectors raise like
     the reference; an index outside the corpus raises ``IndexError``."""
     torch = _native.require_gpu()
-
-    def dev(a, dtype):
-        if isinstance(a, torch.Tensor):
-            return a if a.is_cuda else a.cuda()
-        return _upload(torch, np.asarray(a, dtype=dtype))
-
-    d_q, d_c, d_i = dev(queries, np.float32), dev(corpus, np.float32), dev(cand_idx, np.int64)
+    d_q = _on_device(torch, queries, np.float32)
+    d_c = _on_device(torch, corpus, np.float32)
+    d_i = _on_device(torch, cand_idx, np.int64)
     scores, status, qstatus = cosine_scores_device(d_c, d_q, d_i)
-    valid = d_i >= 0
-    if bool((qstatus != 0).any()) or bool(((status == 1) & valid).any()):
-        raise ValueError("Cannot normalize zero vector")
-    if bool(((status == 2) & valid).any()):
-        raise IndexError("candidate index out of range of the corpus")
+    _raise_for_status(status, qstatus, valid=d_i >= 0)
     order, sorted_scores = topk_desc_device(scores, int(d_i.shape[1]))
     return order.cpu().numpy(), sorted_scores.cpu().numpy()
 

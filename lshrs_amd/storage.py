@@ -91,20 +91,27 @@ class InMemoryStorage:
         through :meth:`get_buckets_many` rather than one :meth:`get_bucket` per band."""
         return bool(self._segments)
 
-    def array_segments(self, band_bytes: int):
-        """For a device mirror of the index (``lshrs_amd/_query_device.py``): the array segments holding keys of this width -
-        a snapshot of the list; the segments themselves are never modified in place, only replaced - provided EVERY bucket of
-        the store lives in such segments (no op-tuple buckets, no keys wider than 6 bytes); else None: the caller reads
-        buckets through :meth:`get_bucket`.  An empty store gives ``[]``."""
+    def array_segments_snapshot(self, band_bytes: int):
+        """For a device mirror of the index (``lshrs_amd/_query_device.py``): ``(segments, token)`` under ONE acquisition of the
+        lock.  ``segments``: the array segments holding keys of this width - a snapshot of the list; the segments themselves are
+        never modified in place, only replaced - provided EVERY bucket of the store lives in such segments (no op-tuple
+        buckets, no keys wider than 6 bytes); else None: the caller reads buckets through :meth:`get_bucket`.  An empty store
+        gives ``[]``.  ``token``: what :meth:`array_segments_token` says of exactly this state (after the fold of too many
+        segments, before any change that waits for the lock): the answer may be kept beside it."""
         with self._lock:
             if len(self._segments) > self.compact_above:
                 self._compact_locked()
+            token = self.array_segments_token()
             if any(self._buckets.values()) or band_bytes > 6:
-                return None
+                return None, token
             segs = [s for s in self._segments if len(s)]
             if any(s.codes is None for s in segs):
-                return None
-            return [s for s in segs if s.band_bytes == band_bytes]
+                return None, token
+            return [s for s in segs if s.band_bytes == band_bytes], token
+
+    def array_segments(self, band_bytes: int):
+        """The segments of :meth:`array_segments_snapshot`."""
+        return self.array_segments_snapshot(band_bytes)[0]
 
     def array_segments_token(self):
         """Something that changes whenever :meth:`array_segments` could answer differently - or None where every call must ask

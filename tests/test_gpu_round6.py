@@ -193,6 +193,40 @@ def test_one_query_per_call_follows_the_store_through_its_changes():
     assert idx2.get_top_k(data[4050], topk=1) == [4050] and idx.get_top_k(data[4050], topk=1) != [4050]
 
 
+def test_an_ingest_that_lands_behind_the_snapshot_is_seen_by_the_next_call():
+    """the device table of the store's segments is kept beside the token that came back WITH the snapshot
+    of the segments.  Here a second segment is stored between the snapshot and its use - what an `index()` on another thread does,
+    without threads and without timing: the call in flight may answer from either state, the next one sees ids 2000..3999.
+    (Keyed by a token read after the snapshot, the old segment list stayed filed under the new token and every later call answered
+    from it: `get_top_k(data[3000], topk=1)` gave [1197], the nearest of ids 0..1999 - profiles/query_refactor_ab.json,
+    `defect_at_parent`.)"""
+    from lshrs_amd import LSHRS, InMemoryStorage
+    from lshrs_amd.packed_ops import bucket_csr
+
+    rng = np.random.default_rng(12)
+    dim = 64
+    data = rng.standard_normal((4000, dim)).astype(np.float32)
+
+    class IngestBehindTheSnapshot(InMemoryStorage):
+        pending = None
+
+        def array_segments_snapshot(self, band_bytes):
+            got = super().array_segments_snapshot(band_bytes)
+            if self.pending is not None:
+                csr, self.pending = self.pending, None
+                self.batch_add_csr(csr)
+            return got
+
+    store = IngestBehindTheSnapshot()
+    idx = LSHRS(dim=dim, num_perm=64, storage=store, packed_ingest=True)
+    idx.index(np.arange(2000), data[:2000])
+    store.pending = bucket_csr(np.arange(2000, 4000), idx._hasher.hash_batch_packed(data[2000:4000]))
+    idx.get_top_k(data[3000], topk=1)                                # the call in flight: either state
+    assert store.pending is None and len(store._segments) == 2
+    assert idx.get_top_k(data[3000], topk=1) == [3000]
+    assert idx.get_top_k(data[10], topk=1) == [10] and idx.get_top_k(data[3999], topk=1) == [3999]
+
+
 def test_vectors_that_live_on_the_gpu_are_indexed_where_they_are():
     """Round 6: `index(ids, x)` with a torch tensor on the GPU - the same buckets as the same rows from host memory (whole and
     ragged chunks, a strided view, float64), the reference's errors at the reference's rows (a zero vector: the rows in front of

@@ -351,6 +351,50 @@ def test_array_collision_counting_equals_the_per_member_loop(monkeypatch, packed
     assert max(len(m) for m in many) > 50
 
 
+def test_the_cut_is_the_references_scalar_rule():
+    """`check_cut` / `keep_counts` (the one copy of the argument errors and of the cut) against the reference's scalar rule
+    (lshrs/core/main.py:617-657): `max(1, ceil(n * p))`, then `min(., k)`, nothing of an empty list."""
+    import math
+
+    from lshrs_amd._query_host import check_cut, keep_counts
+
+    lens = np.arange(51)
+    for k in (None, 1, 7):
+        check_cut(k, None)
+        assert keep_counts(lens, k, None).tolist() == [n if k is None else min(n, k) for n in range(51)]
+        for p in (1e-9, 0.1, 0.5, 0.95, 1.0):
+            check_cut(k, p)
+            want = [0 if n == 0 else (max(1, math.ceil(n * p)) if k is None else min(max(1, math.ceil(n * p)), k))
+                    for n in range(51)]
+            got = keep_counts(lens, k, p)
+            assert got.dtype == np.int64 and got.tolist() == want
+            assert [int(keep_counts(n, k, p)) for n in range(51)] == want            # (one list: the one-vector flow)
+    for k, p, message in ((0, None, "top_k must be greater than zero"), (-3, 0.5, "top_k must be greater than zero"),
+                          (5, 0.0, "top_p must be within the range"), (5, 1.5, "top_p must be within the range"),
+                          (0, 2.0, "top_p must be within the range"), (None, -0.1, "top_p must be within the range")):
+        with pytest.raises(ValueError, match=message):
+            check_cut(k, p)
+
+
+def test_fetch_table_stacks_the_lists_and_names_a_bad_fetch():
+    from lshrs_amd._query_host import fetch_table
+
+    data = np.arange(40, dtype=np.float64).reshape(10, 4)
+    asked = []
+
+    def fetch(ids):
+        asked.append(ids)
+        return data[np.asarray(ids)]
+
+    ids, bounds = np.array([3, 1, 7, 7, 0, 9], dtype=np.int64), np.array([0, 2, 2, 5, 6, 6], dtype=np.int64)
+    table = fetch_table(fetch, 4, ids, bounds)
+    assert table.dtype == np.float32 and np.array_equal(table, data[ids]) and asked == [[3, 1], [7, 7, 0], [9]]
+    with pytest.raises(ValueError, match=r"Fetched vectors must have shape \(n, 5\); received \(2, 4\)"):
+        fetch_table(fetch, 5, ids, bounds)
+    with pytest.raises(ValueError, match=r"mismatched batch size \(expected 2, received 1\)"):
+        fetch_table(lambda got: data[np.asarray(got[:1])], 4, ids, bounds)
+
+
 @pytest.mark.parametrize("nb,r,buffer_size,prefill", [(4, 4, 1, 0), (4, 4, 7, 2), (16, 4, 100, 3), (3, 5, 16, 1), (8, 2, 10_000, 5),
                                                        (16, 16, 33, 0), (5, 9, 4, 1)])
 def test_op_tuple_windows_are_the_per_vector_loops_batches(monkeypatch, nb, r, buffer_size, prefill):

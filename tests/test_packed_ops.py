@@ -303,9 +303,9 @@ def test_array_buckets_are_sets_like_the_references_redis_sets():
 
 def test_reindexed_ids_rank_like_the_tuple_fed_store():
     """The ordered candidates of a query (collision count, then id: lshrs/core/main.py:614) with ids indexed several
-    times: array-fed == tuple-fed, and no candidate is lost (the packed sort key of `_ordered_candidates_arrays` went
+    times: array-fed == tuple-fed, and no candidate is lost (the packed sort key of `order_candidates` went
     negative when a count exceeded num_bands)."""
-    from lshrs_amd.core import LSHRS
+    from lshrs_amd._query_host import bucket_pairs, order_candidates, split_rows
     from lshrs_amd.packed_ops import _csr_host
     from lshrs_amd.storage import InMemoryStorage
 
@@ -322,14 +322,55 @@ def test_reindexed_ids_rank_like_the_tuple_fed_store():
     a.batch_add_csr(one)
     t.batch_add([(b, keys[i, b].tobytes(), int(v)) for i, v in enumerate((5, 5, 7)) for b in range(nb)])
 
-    class _Shell(LSHRS):                                                  # only the candidate ordering is under test
-        def __init__(self, storage):
-            self._storage = storage
+    def ordered(store):                                                   # only the candidate ordering is under test
+        q, _, m = bucket_pairs(store, keys[:2])
+        ids, bounds = order_candidates(q, m, 2, nb)
+        return split_rows(ids.tolist(), np.diff(bounds))
 
-    got = _Shell(a)._ordered_candidates_many(keys[:2])
-    want = _Shell(t)._ordered_candidates_many(keys[:2])
+    got, want = ordered(a), ordered(t)
     assert got == want and all(len(g) > 0 for g in got)
     assert {10, 5} <= set(got[0])
+
+
+def test_a_snapshot_of_the_array_segments_carries_its_own_token():
+    """`array_segments_snapshot` hands the segments and the change token over from ONE acquisition of the lock: what is kept
+    beside that token describes that state and no later one - the fold of too many segments included - and a store whose
+    token says "ask every time" (dict entries, emptied ones too) says so with the snapshot: such an answer is never kept."""
+    from lshrs_amd.packed_ops import _csr_host
+    from lshrs_amd.storage import InMemoryStorage
+
+    rng = np.random.default_rng(13)
+
+    def segment(lo):
+        return _csr_host(np.arange(lo, lo + 40, dtype=np.int64), rng.integers(0, 4, size=(40, 3, 2), dtype=np.uint8))
+
+    store = InMemoryStorage()
+    assert store.array_segments_snapshot(2) == ([], store.array_segments_token())
+    store.batch_add_csr(segment(0))
+    segs, token = store.array_segments_snapshot(2)
+    assert token is not None and token == store.array_segments_token() and len(segs) == 1
+    assert [id(s) for s in store.array_segments(2)] == [id(s) for s in segs]
+    store.batch_add_csr(segment(100))
+    assert store.array_segments_token() != token and len(segs) == 1          # the token handed over stays that snapshot's
+    assert len(store.array_segments(2)) == 2 and store.array_segments(3) == []
+    # more segments than a lookup tolerates: folded under the same acquisition - segments and token are both of the folded state
+    store.compact_above = 4
+    for lo in range(200, 800, 100):
+        store.batch_add_csr(segment(lo))
+    assert len(store._segments) == 8
+    before = store.array_segments_token()
+    segs, token = store.array_segments_snapshot(2)
+    assert len(segs) == 1 and len(store._segments) == 1 and segs[0] is store._segments[0]
+    assert token == store.array_segments_token() != before
+    assert sorted(segs[0].members.tolist()) == sorted(np.r_[tuple(np.arange(lo, lo + 40) for lo in range(0, 800, 100))].tolist() * 3)
+    # an op-tuple bucket: no segment list and no token; emptied again: the segments, still without a token
+    store.batch_add([(0, b"\x01\x02", 5000)])
+    assert store.array_segments_token() is None and store.array_segments_snapshot(2) == (None, None)
+    store.remove_indices([5000])
+    assert store.array_segments_token() is None
+    segs, token = store.array_segments_snapshot(2)
+    assert token is None and len(segs) == 1
+    assert store.array_segments_snapshot(7) == (None, None)                  # (keys wider than the codes: get_bucket)
 
 
 def test_redis_writer_opens_a_new_pipeline_every_buffer_size_members():
