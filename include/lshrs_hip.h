@@ -541,6 +541,34 @@ int lshrs_cosine_ragged_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int3
                             const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
                             float* scores, int32_t* err, void* stream);
 
+/* The same two forms on a corpus stored in 8 bits: int8 (_i8) or OCP fp8 e4m3fn (_f8e4m3: 1 sign, 4 exponent bits of bias 7,
+ * 3 mantissa bits; 0x7f / 0xff NaN, no infinity - not MI300's fnuz), (m, dim) with row stride ldc in elements (= bytes), any
+ * byte address.  Every element is converted to f32 exactly (e4m3 subnormals included) and scored in f32 as above: the f32
+ * entries' scores, statuses and err bits on the upcast corpus; a row holding an e4m3 NaN scores NaN with status 0, as the f32
+ * entries do.  A row's scale is not needed: cos(q, s * x) = cos(q, x) for s > 0 (lshrs_quantize_rows_*). */
+int lshrs_cosine_batch_i8(const int8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                          const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus,
+                          void* stream);
+int lshrs_cosine_batch_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                              const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus,
+                              void* stream);
+int lshrs_cosine_ragged_i8(const int8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                           const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
+                           float* scores, int32_t* err, void* stream);
+int lshrs_cosine_ragged_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                               const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
+                               float* scores, int32_t* err, void* stream);
+
+/* Rows of an f32 matrix X (n, dim), row stride ldx, to 8-bit codes in out (n, dim), row stride ldo (elements), each row with
+ * its own symmetric scale: s = Q / max|x| (one f32 division; Q = 127 for int8, 448 for e4m3fn), code = x * s rounded to
+ * nearest-even - int8 clamped to [-127, 127] (never -128), e4m3fn in the OCP encoding (never NaN).  The scale is not kept:
+ * the cosine entries above need none.  status u8 (n,), required: 0 written (a zero row stays zero); 1 the row holds an inf or
+ * a NaN, 2 max|x| is so small that Q / max|x| overflows f32 - both written as zeros. */
+int lshrs_quantize_rows_i8(const float* X, int64_t n, int64_t ldx, int32_t dim, int8_t* out, int64_t ldo, uint8_t* status,
+                           void* stream);
+int lshrs_quantize_rows_f8e4m3(const float* X, int64_t n, int64_t ldx, int32_t dim, uint8_t* out, int64_t ldo,
+                               uint8_t* status, void* stream);
+
 /* Per query the first keep[qi] candidates in descending score (ties: ascending position in the list; NaN last - the order of
  * lshrs_topk_desc_f32) into the compact arrays out_ids / out_scores at out_off[qi]; lists and scores at pair_off[qi], ucount[qi]
  * long; a list longer than max_candidates (<= LSHRS_QUERY_MAX_PAIRS: the LDS network) is left to the caller (lshrs_topk_desc_f32

@@ -175,11 +175,16 @@ def _declare(lib: ctypes.CDLL) -> None:
     # (corpus, m, ldc, dim, queries, q, cand_rows, row_off, row_cnt, total, scores, err, stream)
     lib.lshrs_cosine_ragged_f32.argtypes = [vp, i64, i64, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp]
     lib.lshrs_cosine_ragged_f32.restype = c.c_int
-    # the same two forms on a corpus of 16-bit elements (ldc in elements): bf16 / f16 converted exactly to f32
-    for dt in ("bf16", "f16"):
+    # the same two forms on a corpus of 16- or 8-bit elements (ldc in elements): bf16 / f16 / int8 / e4m3fn converted exactly
+    # to f32
+    for dt in ("bf16", "f16", "i8", "f8e4m3"):
         batch, ragged = getattr(lib, "lshrs_cosine_batch_" + dt), getattr(lib, "lshrs_cosine_ragged_" + dt)
         batch.argtypes, batch.restype = lib.lshrs_cosine_batch_f32.argtypes, c.c_int
         ragged.argtypes, ragged.restype = lib.lshrs_cosine_ragged_f32.argtypes, c.c_int
+    # (X, n, ldx, dim, out, ldo, status, stream): f32 rows to 8-bit codes, a scale of their own per row
+    for dt in ("i8", "f8e4m3"):
+        quant = getattr(lib, "lshrs_quantize_rows_" + dt)
+        quant.argtypes, quant.restype = [vp, i64, i64, i32, vp, i64, vp, vp], c.c_int
     # (cand_ids, scores, pair_off, ucount, keep, out_off, q, max_candidates, out_ids, out_scores, done_host, epoch, stream)
     lib.lshrs_query_rank_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
     lib.lshrs_query_rank_f32.restype = c.c_int
@@ -229,6 +234,12 @@ EXPORTS = (
     "lshrs_cosine_batch_f16",
     "lshrs_cosine_ragged_bf16",
     "lshrs_cosine_ragged_f16",
+    "lshrs_cosine_batch_i8",
+    "lshrs_cosine_batch_f8e4m3",
+    "lshrs_cosine_ragged_i8",
+    "lshrs_cosine_ragged_f8e4m3",
+    "lshrs_quantize_rows_i8",
+    "lshrs_quantize_rows_f8e4m3",
     "lshrs_query_rank_f32",
     "lshrs_pipe_create",
     "lshrs_pipe_destroy",

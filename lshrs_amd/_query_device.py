@@ -246,7 +246,7 @@ def rank_and_cut(lists: _Lists, top_k: Optional[int], top_p: Optional[float], *,
                  cand_rows=None) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
     """The ranked, cut answer of every query as arrays ``(ids, scores or None, bounds)``: query i's ids are
     ``ids[bounds[i]:bounds[i + 1]]``.  ``top_p`` None: the collision order, first ``top_k`` (lshrs/core/main.py:619-625).
-    Else the candidates scored against ``corpus`` (device (m, dim) float32, bfloat16 or float16 -
+    Else the candidates scored against ``corpus`` (device (m, dim) float32, bfloat16, float16, int8 or float8_e4m3fn -
     ``similarity.corpus_entry``; row = ``cand_rows`` entry, default the id itself), ordered by score, cut to
     ``max(1, ceil(n * top_p))`` and ``top_k`` (:646-657)."""
     torch = _native.require_gpu()

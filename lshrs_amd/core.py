@@ -432,7 +432,7 @@ class LSHRS:
         corpus = self._corpus
         if rerank:
             try:
-                corpus_entry(corpus, "ragged", self._dim)       # a device corpus the rerank reads as it is (float32 / bf16 / f16)
+                corpus_entry(corpus, "ragged", self._dim)       # a device corpus the rerank reads as it is (f32 / 16 / 8 bits)
             except ValueError:
                 return None
         dev = corpus.device if rerank else h._torch_device()
@@ -469,12 +469,13 @@ class LSHRS:
         return list(self.query(vector, top_k=None, top_p=p))  # type: ignore[arg-type]
 
     def set_corpus(self, corpus) -> None:
-        """Attach the indexed vectors as a device-resident ``(m, dim)`` float32, bfloat16 or float16 tensor whose row ``i``
-        is the vector of id ``i``: ``query`` / ``get_above_p`` / ``query_many`` then gather their candidates from it on the
-        device instead of calling ``vector_fetch_fn`` (lshrs/core/main.py:629-646 fetches and stacks them on the host).
-        16-bit rows are converted to float32 exactly inside the rerank: the scores are those of ``corpus.float()`` (the
-        reference's ``np.asarray(fetch(ids), dtype=np.float32)``), at half the memory and half the bytes gathered.
-        ``None`` detaches."""
+        """Attach the indexed vectors as a device-resident ``(m, dim)`` float32, bfloat16, float16, int8 or float8_e4m3fn
+        tensor whose row ``i`` is the vector of id ``i``: ``query`` / ``get_above_p`` / ``query_many`` then gather their
+        candidates from it on the device instead of calling ``vector_fetch_fn`` (lshrs/core/main.py:629-646 fetches and stacks
+        them on the host).  16- and 8-bit rows are converted to float32 exactly inside the rerank: the scores are those of
+        ``corpus.float()`` (the reference's ``np.asarray(fetch(ids), dtype=np.float32)``), at half / a quarter of the memory
+        and of the bytes gathered.  ``lshrs_amd.quantize_rows`` makes the 8-bit rows (a scale per row, which a cosine does
+        not see).  ``None`` detaches."""
         if corpus is not None and (getattr(corpus, "ndim", 0) != 2 or int(corpus.shape[1]) != self._dim):
             raise ValueError(f"corpus must have shape (m, {self._dim})")
         self._corpus = corpus
@@ -489,10 +490,10 @@ class LSHRS:
 
         ``vectors``: ``(n, dim)`` array-like as in the reference - or a torch tensor that already lives on a GPU (round 6: the
         queries then never cross the link; 10 000 x 768 are 30 MB = 0.7 of the 2.7 ms a reranked batch takes).
-        ``corpus``: optional device-resident ``(m, dim)`` float32, bfloat16 or float16 tensor whose row ``i`` is the vector
-        of id ``i`` (default: what :meth:`set_corpus` attached); with it the candidates are gathered on the device and
-        ``vector_fetch_fn`` is not called (16-bit rows are converted to float32 exactly: the scores of ``corpus.float()``;
-        another dtype raises ``ValueError``).
+        ``corpus``: optional device-resident ``(m, dim)`` float32, bfloat16, float16, int8 or float8_e4m3fn tensor whose row
+        ``i`` is the vector of id ``i`` (default: what :meth:`set_corpus` attached); with it the candidates are gathered on
+        the device and ``vector_fetch_fn`` is not called (16- and 8-bit rows are converted to float32 exactly: the scores of
+        ``corpus.float()``; another dtype raises ``ValueError``).
         ``return_arrays``: ``(ids, scores, bounds)`` instead of lists - query ``i``'s answer is ``ids[bounds[i]:bounds[i + 1]]``
         (int64) with ``scores[...]`` (float32; ``None`` without ``top_p``): no Python object per result.
         ``engine``: "auto" (the device path wherever the hasher is the HIP one; a batch with a candidate list beyond the

@@ -20,6 +20,10 @@ namespace {
 // f32 exactly in registers, every product and sum stays an f32 FMA against the f32 query; a
 // 16-B load holds 8 elements, and eight rows are in flight to keep the bytes per wave of f32
 // (their indices and row pointers in scalar registers: 114 VGPRs, four waves per SIMD).
+// A corpus stored in 8 bits (int8 / OCP fp8 e4m3fn) likewise: a 16-B load holds 16 elements and
+// sixteen rows are in flight, the bytes per wave of f32 and of 16 bits again (152 / 164 VGPRs,
+// three waves per SIMD).  Its 32 sums are reduced together and 16 lanes finish the 16 rows at
+// once: with a wave_sum and a lane-0 epilogue per row the 8-bit kernel was no faster than bf16.
 // ------------------------------------------------------------------------------------------
 constexpr int kCosThreads = 256;
 constexpr int kCosWaves = kCosThreads / 64;
@@ -27,6 +31,8 @@ constexpr int kCosInflight = 4;
 
 struct Bf16 {};   // element tags of a 16-bit corpus (rows of uint16_t)
 struct F16 {};
+struct I8 {};     // element tags of an 8-bit corpus (rows of int8_t / uint8_t)
+struct F8E4M3 {};
 
 // per element type: what a row holds, rows in flight per wave, elements per 16-B load
 template <typename E> struct CosElem {
@@ -39,6 +45,16 @@ template <> struct CosElem<float> {
   static constexpr int kInflight = kCosInflight;
   static constexpr int kVec = 4;
 };
+template <> struct CosElem<I8> {
+  using T = int8_t;
+  static constexpr int kInflight = 4 * kCosInflight;
+  static constexpr int kVec = 16;
+};
+template <> struct CosElem<F8E4M3> {
+  using T = uint8_t;
+  static constexpr int kInflight = 4 * kCosInflight;
+  static constexpr int kVec = 16;
+};
 
 // exact conversions: the element in the low / high half of a dword, and a lone 16-bit element
 __device__ __forceinline__ float elem_lo(Bf16, uint32_t w) { return __uint_as_float(w << 16); }
@@ -47,6 +63,23 @@ __device__ __forceinline__ float elem_lo(F16, uint32_t w) { return (float)__buil
 __device__ __forceinline__ float elem_hi(F16, uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
 template <typename E>
 __device__ __forceinline__ float elem(uint16_t bits) { return elem_lo(E{}, bits); }
+
+// exact conversions of 8-bit elements: the four bytes of a dword (in memory order), and a lone byte.  e4m3fn goes through
+// gfx950's fp8 conversion, which reads the OCP encoding (not MI300's fnuz): subnormals kept, 0x7f / 0xff -> NaN.
+__device__ __forceinline__ void elem4(I8, uint32_t w, float (&x)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) x[j] = (float)(int8_t)(w >> (8 * j));
+}
+__device__ __forceinline__ void elem4(F8E4M3, uint32_t w, float (&x)[4]) {
+  // (one conversion per byte, like int8's: each result feeds a packed FMA as it is - the pairwise conversion's pairs would
+  // have to be taken apart first)
+  x[0] = __builtin_amdgcn_cvt_f32_fp8((int)w, 0);
+  x[1] = __builtin_amdgcn_cvt_f32_fp8((int)w, 1);
+  x[2] = __builtin_amdgcn_cvt_f32_fp8((int)w, 2);
+  x[3] = __builtin_amdgcn_cvt_f32_fp8((int)w, 3);
+}
+__device__ __forceinline__ float elem1(I8, int8_t b) { return (float)b; }
+__device__ __forceinline__ float elem1(F8E4M3, uint8_t b) { return __builtin_amdgcn_cvt_f32_fp8((int)b, 0); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -57,7 +90,8 @@ __device__ __forceinline__ float wave_sum(float v) {
 // RAGGED (ABI 7, lshrs_cosine_ragged_f32): query qi has row_cnt[qi] candidates, listed - and scored - at row_off[qi] of the
 // flat cand_idx / scores arrays (the candidate lists of a batch of LSH queries, lshrs/core/main.py:629-646); what is wrong with
 // a candidate is OR-ed into err[0] (1 zero norm, 2 index outside the corpus) instead of a status byte per candidate.
-// E: float, Bf16 or F16 - the corpus's element type (ldc in elements); queries, scores and status are f32 / u8 for all three.
+// E: float, Bf16, F16, I8 or F8E4M3 - the corpus's element type (ldc in elements); queries, scores and status are f32 / u8 for
+// all of them.
 template <typename E, bool ALIGNED, bool RAGGED>
 __global__ __launch_bounds__(kCosThreads) void cosine_kernel(const typename CosElem<E>::T* __restrict__ corpus, int64_t m,
                                                              int64_t ldc, int dim, const float* __restrict__ queries,
@@ -69,8 +103,8 @@ __global__ __launch_bounds__(kCosThreads) void cosine_kernel(const typename CosE
   extern __shared__ __attribute__((aligned(16))) float qlds[];  // dim floats (+ pad to 4) + kCosWaves partials
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  // (16-bit rows: the wave index said to be wave-uniform, so that a wave's candidate indices and row pointers sit in scalar
-  // registers - eight rows in flight then leave the vector registers for the data)
+  // (16- and 8-bit rows: the wave index said to be wave-uniform, so that a wave's candidate indices and row pointers sit in scalar
+  // registers - eight / sixteen rows in flight then leave the vector registers for the data)
   const int wave = std::is_same_v<E, float> ? tid >> 6 : __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qi = blockIdx.x / slices;
   const int slice = blockIdx.x % slices;
@@ -151,6 +185,46 @@ __global__ __launch_bounds__(kCosThreads) void cosine_kernel(const typename CosE
           }
         }
       }
+    } else if constexpr (sizeof(T) == 1) {
+      if (ALIGNED) {
+        // 16 elements per lane per load (dim, ldc multiples of 16, 16-B aligned base): elements 4e .. 4e+3 of the 16 are the
+        // bytes of dword e, summed in element order
+        for (int k = lane * 16; k < dim; k += 1024) {
+          float qx[16];
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const f32x4 qv4 = *reinterpret_cast<const f32x4*>(qlds + k + 4 * v);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) qx[4 * v + e] = qv4[e];
+          }
+          u32x4 cx[kInflight];
+#pragma unroll
+          for (int u = 0; u < kInflight; ++u) cx[u] = *reinterpret_cast<const u32x4*>(rowp[u] + k);
+#pragma unroll
+          for (int u = 0; u < kInflight; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              float x[4];
+              elem4(E{}, cx[u][e], x);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                dot[u] = __builtin_fmaf(x[j], qx[4 * e + j], dot[u]);
+                nn[u] = __builtin_fmaf(x[j], x[j], nn[u]);
+              }
+            }
+        }
+      } else {
+        // any dim, row stride and byte address: one element per lane per load
+        for (int k = lane; k < dim; k += 64) {
+          const float qx = qlds[k];
+#pragma unroll
+          for (int u = 0; u < kInflight; ++u) {
+            const float cx = elem1(E{}, rowp[u][k]);
+            dot[u] = __builtin_fmaf(cx, qx, dot[u]);
+            nn[u] = __builtin_fmaf(cx, cx, nn[u]);
+          }
+        }
+      }
     } else {
       if (ALIGNED) {
         // 8 elements per lane per load (dim, ldc multiples of 8, 16-B aligned base): element 2e / 2e+1 of the 8 are the
@@ -185,6 +259,47 @@ __global__ __launch_bounds__(kCosThreads) void cosine_kernel(const typename CosE
           }
         }
       }
+    }
+    if constexpr (sizeof(T) == 1) {
+      // 8 bits: the 32 sums of the 16 rows (dot, ||c||^2) reduced together.  At each butterfly step a lane keeps one value of
+      // every pair and sends the other (the same additions as wave_sum's, in the same tree: bit for bit its totals), so the
+      // values per lane halve: 33 exchanges instead of 192.  Then lane L < 32 holds the dot of row bitrev4((L >> 1) & 15),
+      // lane L + 32 its ||c||^2, and 16 lanes finish their rows at once.
+      static_assert(kInflight == 16, "the transposed reduction below is written for 16 rows");
+      float v[2 * kInflight];
+#pragma unroll
+      for (int u = 0; u < kInflight; ++u) { v[2 * u] = dot[u]; v[2 * u + 1] = nn[u]; }
+#pragma unroll
+      for (int s = 0; s < 5; ++s) {
+        const int mask = 32 >> s;
+        const bool hi = (lane & mask) != 0;
+#pragma unroll
+        for (int i = 0; i < (16 >> s); ++i) {
+          const float send = hi ? v[2 * i] : v[2 * i + 1];
+          const float keep = hi ? v[2 * i + 1] : v[2 * i];
+          v[i] = keep + __shfl_xor(send, mask);
+        }
+      }
+      const float d = v[0] + __shfl_xor(v[0], 1);
+      const float s2 = __shfl_xor(d, 32);
+      const int ur = ((lane >> 1) & 1) << 3 | ((lane >> 2) & 1) << 2 | ((lane >> 3) & 1) << 1 | ((lane >> 4) & 1);
+      int code = 3;
+#pragma unroll
+      for (int u = 0; u < kInflight; ++u) code = (u == ur) ? st[u] : code;
+      if ((lane & 33) == 0 && code != 3) {
+        const int64_t o = obase + base + ur;
+        float sc;
+        if (code == 0) {
+          const float cn = sqrtf(s2);
+          if (cn == 0.f) code = 1;
+          sc = d / (cn * qnorm);
+        }
+        if (code != 0) sc = __builtin_nanf("");
+        scores[o] = sc;
+        if (status != nullptr) status[o] = (uint8_t)code;
+        if (RAGGED && code != 0 && err != nullptr) atomicOr(err, code);
+      }
+      continue;
     }
 #pragma unroll
     for (int u = 0; u < kInflight; ++u) {
@@ -225,6 +340,71 @@ __global__ __launch_bounds__(256) void l2_normalize_kernel(const float* __restri
   if (threadIdx.x == 0 && status != nullptr) status[row] = (norm == 0.f) ? 1 : 0;
   float* o = out + row * (int64_t)dim;
   for (int k = threadIdx.x; k < dim; k += 256) o[k] = x[k] / norm;
+}
+
+// ------------------------------------------------------------------------------------------
+// quantize_rows: an f32 row to 8-bit codes with its own symmetric scale, one workgroup per row.
+// s = Q / max|x| (one f32 division), code = x * s rounded to nearest-even.  The scale is not
+// kept: a cosine does not see it.  status: 0 written; 1 a non-finite element, 2 max|x| so small
+// that Q / max|x| overflows - both rows written as zeros.  A zero row stays zero (status 0).
+// ------------------------------------------------------------------------------------------
+template <typename E> struct QuantCode;
+template <> struct QuantCode<I8> {
+  static constexpr float kQ = 127.f;
+  __device__ static int8_t encode(float v) {       // clamped to [-127, 127]: -128 is never written
+    return (int8_t)fminf(fmaxf(__builtin_rintf(v), -127.f), 127.f);
+  }
+};
+template <> struct QuantCode<F8E4M3> {
+  static constexpr float kQ = 448.f;
+  // OCP e4m3fn, round to nearest-even; |v| <= 448 up to the rounding of x * s, never NaN
+  __device__ static uint8_t encode(float v) {
+    const uint32_t u = __float_as_uint(v) & 0x7fffffffu;
+    const uint32_t sign = (__float_as_uint(v) >> 24) & 0x80u;
+    uint32_t code;
+    if (u < 0x3c800000u)                      // below 2^-6: multiples of 2^-9 (code 8 = 2^-6, the least normal)
+      code = (uint32_t)__builtin_rintf(__uint_as_float(u) * 512.f);
+    else                                      // 3 mantissa bits kept, ties to even; a carry moves into the exponent
+      code = ((u + 0x7ffffu + ((u >> 20) & 1u)) >> 20) - (120u << 3);
+    return (uint8_t)(sign | min(code, 0x7eu));  // (0x7e = 448, the largest finite code)
+  }
+};
+
+template <typename E>
+__global__ __launch_bounds__(256) void quantize_rows_kernel(const float* __restrict__ X, int64_t ldx, int dim,
+                                                            typename CosElem<E>::T* __restrict__ out, int64_t ldo,
+                                                            uint8_t* __restrict__ status) {
+  __shared__ float pmax[4];
+  __shared__ int pbad[4];
+  const int64_t row = blockIdx.x;
+  const float* x = X + row * ldx;
+  float amax = 0.f;
+  int bad = 0;
+  for (int k = threadIdx.x; k < dim; k += 256) {
+    const float a = fabsf(x[k]);
+    bad |= !(a <= __FLT_MAX__);               // (inf and NaN)
+    amax = fmaxf(amax, a);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    amax = fmaxf(amax, __shfl_xor(amax, off));
+    bad |= __shfl_xor(bad, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    pmax[threadIdx.x >> 6] = amax;
+    pbad[threadIdx.x >> 6] = bad;
+  }
+  __syncthreads();
+  amax = fmaxf(fmaxf(pmax[0], pmax[1]), fmaxf(pmax[2], pmax[3]));
+  bad = pbad[0] | pbad[1] | pbad[2] | pbad[3];
+  const float s = __fdiv_rn(QuantCode<E>::kQ, amax);
+  const int code = bad ? 1 : (amax != 0.f && !(s <= __FLT_MAX__)) ? 2 : 0;
+  if (threadIdx.x == 0) status[row] = (uint8_t)code;
+  auto* o = out + row * ldo;
+  for (int k = threadIdx.x; k < dim; k += 256) {
+    const float v = (code == 0 && amax != 0.f) ? x[k] * s : 0.f;
+    o[k] = QuantCode<E>::encode(v);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -363,8 +543,8 @@ int lshrs_sort_u64_rows(uint64_t* items, int q, int64_t cpad, hipStream_t s) {
 }
 
 namespace {
-// The launchers behind the six lshrs_cosine_{batch,ragged}_{f32,bf16,f16} entries: argument checks (before anything touches a
-// device), slicing and the choice of the aligned path, written once for every corpus element type.
+// The launchers behind the ten lshrs_cosine_{batch,ragged}_{f32,bf16,f16,i8,f8e4m3} entries: argument checks (before anything
+// touches a device), slicing and the choice of the aligned path, written once for every corpus element type.
 template <typename E>
 int cosine_batch(const typename CosElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
                  const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus, void* stream) {
@@ -421,6 +601,18 @@ int cosine_ragged(const typename CosElem<E>::T* corpus, int64_t m, int64_t ldc, 
                        scores, nullptr, nullptr, row_off, row_cnt, err);
   return -(int)hipGetLastError();
 }
+
+template <typename E>
+int quantize_rows(const float* X, int64_t n, int64_t ldx, int32_t dim, typename CosElem<E>::T* out, int64_t ldo,
+                  uint8_t* status, void* stream) {
+  if (n == 0) return 0;
+  if (X == nullptr || out == nullptr || status == nullptr || n < 0 || dim <= 0 || ldx < dim || ldo < dim)
+    return LSHRS_E_BADARG;
+  if (n > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
+  hipLaunchKernelGGL(quantize_rows_kernel<E>, dim3((unsigned)n), dim3(256), 0, static_cast<hipStream_t>(stream), X, ldx, dim,
+                     out, ldo, status);
+  return -(int)hipGetLastError();
+}
 }  // namespace
 
 extern "C" {
@@ -459,6 +651,40 @@ int lshrs_cosine_ragged_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int3
                             const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
                             float* scores, int32_t* err, void* stream) {
   return cosine_ragged<F16>(corpus, m, ldc, dim, queries, q, cand_rows, row_off, row_cnt, total, scores, err, stream);
+}
+
+int lshrs_cosine_batch_i8(const int8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                          const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus,
+                          void* stream) {
+  return cosine_batch<I8>(corpus, m, ldc, dim, queries, q, cand_idx, c, scores, status, qstatus, stream);
+}
+
+int lshrs_cosine_batch_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                              const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus,
+                              void* stream) {
+  return cosine_batch<F8E4M3>(corpus, m, ldc, dim, queries, q, cand_idx, c, scores, status, qstatus, stream);
+}
+
+int lshrs_cosine_ragged_i8(const int8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                           const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
+                           float* scores, int32_t* err, void* stream) {
+  return cosine_ragged<I8>(corpus, m, ldc, dim, queries, q, cand_rows, row_off, row_cnt, total, scores, err, stream);
+}
+
+int lshrs_cosine_ragged_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                               const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total,
+                               float* scores, int32_t* err, void* stream) {
+  return cosine_ragged<F8E4M3>(corpus, m, ldc, dim, queries, q, cand_rows, row_off, row_cnt, total, scores, err, stream);
+}
+
+int lshrs_quantize_rows_i8(const float* X, int64_t n, int64_t ldx, int32_t dim, int8_t* out, int64_t ldo, uint8_t* status,
+                           void* stream) {
+  return quantize_rows<I8>(X, n, ldx, dim, out, ldo, status, stream);
+}
+
+int lshrs_quantize_rows_f8e4m3(const float* X, int64_t n, int64_t ldx, int32_t dim, uint8_t* out, int64_t ldo,
+                               uint8_t* status, void* stream) {
+  return quantize_rows<F8E4M3>(X, n, ldx, dim, out, ldo, status, stream);
 }
 
 int lshrs_l2_normalize_f32(const float* X, int64_t n, int64_t ldx, int32_t dim, float* out, uint8_t* status,

@@ -1,10 +1,14 @@
-"""The cosine rerank on a device corpus stored in float32, bfloat16 and float16 - BASELINE config 3's rerank: a 1M x 768
-corpus, 10 000 queries x 1 000 candidates (the candidate table of tools/rerank_repro.py).
+"""The cosine rerank on a device corpus stored in float32, bfloat16, float16, int8 and float8_e4m3fn - BASELINE config 3's
+rerank: a 1M x 768 corpus, 10 000 queries x 1 000 candidates (the candidate table of tools/rerank_repro.py).  The 16-bit
+corpora are the f32 rows rounded, the 8-bit ones the f32 rows through quantize_rows (a scale per row).
 
 Per corpus dtype, in one process:
-  kernel   lshrs_cosine_ragged_{f32,bf16,f16} timed by HIP events, the three dtypes interleaved launch by launch (drift between
-           them cancels), median of --launches each; candidates/s and the bytes a candidate needs (row + 8-B index + 4-B score:
-           4 * dim + 12 for f32, 2 * dim + 12 for 16 bits) as a fraction of 8 TB/s
+  kernel   lshrs_cosine_ragged_{f32,bf16,f16,i8,f8e4m3} timed by HIP events, the dtypes interleaved launch by launch (drift
+           between them cancels), median of --launches each; candidates/s and the bytes a candidate needs (row + 8-B index +
+           4-B score: element bytes * dim + 12) as a fraction of 8 TB/s; the largest score difference against the f32 kernel
+           on the original rows (for 8 bits: the quantization's effect) and against the f32 kernel on corpus.float() (the
+           kernel's own error)
+  quantize quantize_rows' time on the 1M x 768 rows (median of 5) and the drift it brings, 1 - cos(row, quantized row)
   api      LSHRS.query_many(top_k=None, top_p=0.5, return_arrays=True) of the 10 000 queries against the corpus indexed under
            id = row, with that corpus attached (set_corpus): queries/s from host arrays and from queries already on the GPU
            (best of --reps, dtypes in rotating order)
@@ -28,7 +32,8 @@ import numpy as np  # noqa: E402
 
 M, DIM, Q, C = 1_000_000, 768, 10_000, 1_000
 PEAK = 8.0e12
-DTYPES = ("float32", "bfloat16", "float16")
+DTYPES = ("float32", "bfloat16", "float16", "int8", "float8_e4m3fn")
+EIGHT = ("int8", "float8_e4m3fn")
 
 
 def main() -> int:
@@ -44,7 +49,7 @@ def main() -> int:
     if not torch.cuda.is_available():
         raise SystemExit("rerank_dtype_bench: no GPU visible - this tool measures the MI355X and has no CPU fallback")
     from lshrs_amd import _native
-    from lshrs_amd.similarity import corpus_entry
+    from lshrs_amd.similarity import corpus_entry, quantize_rows
 
     lib = _native.load()
     dev = torch.device("cuda:0")
@@ -54,6 +59,30 @@ def main() -> int:
     for lo in range(0, M, 250_000):
         f32[lo:lo + 250_000] = torch.randn(250_000, DIM, device=dev, generator=gen)
     corpora = {"float32": f32, "bfloat16": f32.to(torch.bfloat16), "float16": f32.to(torch.float16)}
+    quantize = {}
+    for kind in EIGHT:
+        dt = getattr(torch, kind)
+        corpora[kind] = quantize_rows(f32, dt)                     # (also the warm-up of the timed calls below)
+        ts = []
+        for _ in range(5):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            again = quantize_rows(f32, dt)
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+            assert torch.equal(again.view(torch.uint8), corpora[kind].view(torch.uint8))
+        del again
+        # 1 - cos(row, quantized row), in float64
+        drift = []
+        for lo in range(0, M, 125_000):
+            x = f32[lo:lo + 125_000].double()
+            y = corpora[kind][lo:lo + 125_000].double()
+            drift.append(1 - (x * y).sum(1) / (x.norm(dim=1) * y.norm(dim=1)))
+        drift = torch.cat(drift)
+        quantize[kind] = {"median_ms": round(float(np.median(ts)), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4),
+                          "drift_1_minus_cos_mean": float(drift.mean()), "drift_1_minus_cos_max": float(drift.max())}
+        del drift
     rng7, rng8 = np.random.default_rng(7), np.random.default_rng(8)
     qrows = rng7.choice(M, Q, replace=False)
     noise = (0.1 * rng7.standard_normal((Q, DIM))).astype(np.float32)
@@ -65,19 +94,19 @@ def main() -> int:
     scores = {k: torch.empty(Q * C, dtype=torch.float32, device=dev) for k in DTYPES}
     stream = torch.cuda.current_stream(dev).cuda_stream
 
-    def launch(kind):
-        corpus = corpora[kind]
+    def launch(kind, corpus=None, out=None):
+        corpus = corpora[kind] if corpus is None else corpus
         entry = corpus_entry(corpus, "ragged", DIM)
         _native.check(getattr(lib, entry)(corpus.data_ptr(), M, corpus.stride(0), DIM, queries.data_ptr(), Q, rows.data_ptr(),
-                                          row_off.data_ptr(), row_cnt.data_ptr(), Q * C, scores[kind].data_ptr(),
-                                          err.data_ptr(), stream), entry)
+                                          row_off.data_ptr(), row_cnt.data_ptr(), Q * C,
+                                          (scores[kind] if out is None else out).data_ptr(), err.data_ptr(), stream), entry)
 
     for _ in range(4):
         for kind in DTYPES:
             launch(kind)
     ms = {k: [] for k in DTYPES}
     for rnd in range(args.launches):
-        order = DTYPES[rnd % 3:] + DTYPES[:rnd % 3]
+        order = DTYPES[rnd % len(DTYPES):] + DTYPES[:rnd % len(DTYPES)]
         for kind in order:
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
@@ -89,16 +118,26 @@ def main() -> int:
     kernel = {}
     for kind in DTYPES:
         med = float(np.median(ms[kind]))
-        per_cand = (4 if kind == "float32" else 2) * DIM + 8 + 4
+        per_cand = corpora[kind].element_size() * DIM + 8 + 4
         kernel[kind] = {"median_ms": round(med, 4), "min_ms": round(min(ms[kind]), 4), "max_ms": round(max(ms[kind]), 4),
                         "launches": len(ms[kind]), "candidates_per_s": Q * C / (med * 1e-3),
                         "bytes_per_candidate": per_cand, "fraction_of_8TBps": Q * C * per_cand / (med * 1e-3) / PEAK}
-        # the 16-bit scores against the f32 kernel's on the same lists (bf16 / f16 rows are the f32 rows rounded)
+        # the narrower scores against the f32 kernel's on the same lists (bf16 / f16 rows are the f32 rows rounded, the 8-bit
+        # ones quantized) and against the f32 kernel on the upcast corpus (the kernel's own error)
         kernel[kind]["max_abs_diff_vs_f32"] = float((scores[kind] - scores["float32"]).abs().max())
-    for kind in ("bfloat16", "float16"):
+        if kind != "float32":
+            upcast, ref = corpora[kind].float(), torch.empty(Q * C, dtype=torch.float32, device=dev)
+            launch("float32", upcast, ref)
+            torch.cuda.synchronize()
+            kernel[kind]["max_abs_diff_vs_upcast"] = float((scores[kind] - ref).abs().max())
+            del upcast, ref
+    assert int(err.item()) == 0
+    for kind in DTYPES[1:]:
         kernel[kind]["speedup_vs_f32"] = kernel["float32"]["median_ms"] / kernel[kind]["median_ms"]
+    for kind in EIGHT:
+        kernel[kind]["speedup_vs_bf16"] = kernel["bfloat16"]["median_ms"] / kernel[kind]["median_ms"]
     out = {"tool": "rerank_dtype_bench", "device": torch.cuda.get_device_name(dev), "corpus_rows": M, "dim": DIM, "queries": Q,
-           "candidates_per_query": C, "kernel": kernel}
+           "candidates_per_query": C, "kernel": kernel, "quantize_rows_1M_x_768": quantize}
 
     if not args.kernel_only:
         from lshrs_amd import LSHRS, InMemoryStorage
@@ -112,7 +151,7 @@ def main() -> int:
         idx.query_many(q_host[:200], top_k=10)                # (the store's bucket arrays go to the device once)
         api = {k: {} for k in DTYPES}
         for rnd in range(args.reps):
-            for kind in DTYPES[rnd % 3:] + DTYPES[:rnd % 3]:
+            for kind in DTYPES[rnd % len(DTYPES):] + DTYPES[:rnd % len(DTYPES)]:
                 idx.set_corpus(corpora[kind])
                 for form, qs in (("host_arrays", q_host), ("queries_on_gpu", queries)):
                     torch.cuda.synchronize()
