@@ -581,6 +581,46 @@ int lshrs_query_rank_f32(const int64_t* cand_ids, const float* scores, const int
                          const int32_t* keep, const int64_t* out_off, int32_t q, int32_t max_candidates,
                          int64_t* out_ids, float* out_scores, int32_t* done_host, int32_t epoch, void* stream);
 
+/* ---- id -> row table of a device-resident vector store (csrc/idmap.hip; lshrs_amd.DeviceVectors) ----
+ * An open-addressing hash table in DEVICE memory from non-negative int64 ids to row numbers: `slots` (a power of two) slots
+ * of 16 bytes {int64 id, int64 row} at a 16-byte aligned address, an empty slot = {-1, -1} (the caller fills a new table
+ * with 0xff bytes), linear probing from the home slot lshrs_idmap_home_slot names.  Every probe loop ends after `slots`
+ * steps at the latest.  A table that is not 16-byte aligned or whose `slots` is not a power of two, a NULL pointer or a
+ * negative count: LSHRS_E_BADARG, before anything touches a device.  (Additive to ABI 7.)
+ *
+ * lshrs_idmap_bytes: 16 * slots, or LSHRS_E_BADARG.  lshrs_idmap_home_slot: the slot probing for `id` starts at - the
+ * function the kernels call (murmur3's 64-bit finalizer, low bits) -, or LSHRS_E_BADARG (negative id, bad slots).  Both
+ * pure host functions. */
+int64_t lshrs_idmap_bytes(int64_t slots);
+int64_t lshrs_idmap_home_slot(int64_t id, int64_t slots);
+
+/* ids[0 .. n) get rows first_row + i.  Rows only grow (a 64-bit compare-and-swap claims the slot, an atomic maximum sets the
+ * row): an id that occurs several times, in this call or in earlier ones on the stream, ends at its LATEST row.
+ * report int32[4], zeroed by the caller, accumulated: [0] slots newly taken (ids new to the table), [1] ids that became
+ * live (new, or erased before), [2] 1 = a negative id was met (skipped), [3] 1 = an id found no free slot (not inserted). */
+int lshrs_idmap_insert_i64(void* table, int64_t slots, const int64_t* ids, int64_t n, int64_t first_row, int32_t* report,
+                           void* stream);
+
+/* The row of every listed id becomes -1; the id keeps its slot (later probes walk over it, a later insert raises the row
+ * again).  live_count int32[1], zeroed by the caller: += ids that had a row. */
+int lshrs_idmap_erase_i64(void* table, int64_t slots, const int64_t* ids, int64_t n, int32_t* live_count, void* stream);
+
+/* rows[i] = the row of ids[i], -1 where the id is absent, erased or negative.  err int32[1] (optional, zeroed by the
+ * caller): |= 256 (bit 8; beside the bits of lshrs_cosine_ragged_*) when any is. */
+int lshrs_idmap_lookup_i64(const void* table, int64_t slots, const int64_t* ids, int64_t n, int64_t* rows, int32_t* err,
+                           void* stream);
+
+/* The same over candidate lists as the collide step leaves them: query qi's ids at cand_ids[pair_off[qi] .. + ucount[qi])
+ * (ucount[qi] < 0: skipped), rows at the same flat positions of `rows` - what lshrs_cosine_ragged_* takes as cand_rows.
+ * No size is read by the host: `total` (entries the lists span) sizes the launch only, as in lshrs_cosine_ragged_f32. */
+int lshrs_idmap_lookup_ragged_i64(const void* table, int64_t slots, const int64_t* cand_ids, const int64_t* pair_off,
+                                  const int32_t* ucount, int32_t q, int64_t total, int64_t* rows, int32_t* err,
+                                  void* stream);
+
+/* Every live (id, row) of `src` inserted into `dst` (another table: growth, compaction).  report as above ([1]: entries
+ * moved). */
+int lshrs_idmap_rehash(const void* src, int64_t src_slots, void* dst, int64_t dst_slots, int32_t* report, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,10 +18,12 @@ from .hasher import HostBlasNotRecognised, LSHHasher
 from .packed_ops import RedisPackedWriter, group_by_bucket, hex_keys
 from .similarity import cosine_similarity, l2_norm, quantize_rows, rerank_batch, top_k_cosine
 from .storage import BucketOperation, InMemoryStorage
+from .vectors import DeviceVectors
 
 __all__ = [
     "LSHRS", "lshrs", "LSHHasher", "HashSignatures", "top_k_cosine", "cosine_similarity", "l2_norm",
     "rerank_batch", "quantize_rows", "get_optimal_config", "InMemoryStorage", "BucketOperation", "NativeLibraryError",
     "RedisPackedWriter", "group_by_bucket", "hex_keys", "HostBlasNotRecognised",
+    "DeviceVectors",
 ]
 __version__ = "0.1.0"

@@ -53,9 +53,12 @@ class CsrIngest:
     chunk_rows = 131_072       # rows per chunk of the copy / pass / grouping pipeline inside a unit
 
     def __init__(self, hashers: List, sink, zero_error, neg_error, *, max_in_flight: Optional[int] = None,
-                 inline: bool = False) -> None:
+                 inline: bool = False, on_stored=None) -> None:
         self._hashers = list(hashers)
         self._sink = sink
+        # on_stored(ids, rows): called once per unit, in unit order, on the unit's lane thread, with the rows whose buckets the
+        # storage took (those in front of the unit's first bad row) - LSHRS(keep_vectors=...) puts them into its vector store
+        self._on_stored = on_stored
         self._zero_error, self._neg_error = zero_error, neg_error
         lanes = len(self._hashers)
         # inline (one lane, one unit at a time: a single index() call): the unit runs on the caller's thread, no pool at all
@@ -157,6 +160,7 @@ class CsrIngest:
         limit = int(negs[0]) if negs.size else n          # rows from the first negative id on are never stored
         state = {"stop": limit, "error": self._neg_error() if limit < n else None, "committed_to": 0}
         pending: list = []
+        stored = 0                    # rows of this unit whose buckets the storage took
         resident = isinstance(arr, torch.Tensor) and arr.is_cuda      # (vectors that live on a GPU: hashed where they are)
 
         def commit(job, lo, hi):
@@ -207,6 +211,7 @@ class CsrIngest:
             # a unit that ends inside a chunk (zero vector at row `stop`): the rows of that chunk in front of it, once more,
             # synchronously - rare, and the only place the keys of a chunk are needed twice
             stop, done_to = state["stop"], state["committed_to"]
+            stored = done_to
             if state["error"] is not None and not isinstance(state["error"], ValueError):
                 raise state["error"]
             if stop > done_to:
@@ -216,6 +221,7 @@ class CsrIngest:
                     with torch.cuda.device(tail_dev):
                         keys = hasher.hash_batch_packed(arr[done_to:stop])
                         self._sink.batch_add_csr(bucket_csr(ids[done_to:stop], keys, device=tail_dev))
+                        stored = stop
             if state["error"] is not None:
                 unit.prev_done.wait()
                 self._fail(state["error"])
@@ -225,6 +231,11 @@ class CsrIngest:
         finally:
             unit.ids = unit.arr = None
             unit.prev_done.wait()          # (never overtake: a unit is done only when every earlier one is)
+            if self._on_stored is not None and stored > 0:
+                try:
+                    self._on_stored(ids[:stored], arr[:stored])
+                except BaseException as exc:  # noqa: BLE001
+                    self._fail(exc)
             unit.done.set()
             self._slots.release()
 

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 # one translation unit per kernel family (what they share: csrc/lshrs_common.h); pipeline.hip: the native driver of the host-engine route
-UNITS = ("sig_setup", "sig_f32", "sig16", "sig16r", "sig_replay", "sig_small", "sig_split", "storage", "rerank", "query", "pipeline")
+UNITS = ("sig_setup", "sig_f32", "sig16", "sig16r", "sig_replay", "sig_small", "sig_split", "storage", "rerank", "query", "idmap", "pipeline")
 SOURCES = tuple(os.path.join(CSRC, u + ".hip") for u in UNITS)
 SOURCE = SOURCES[0]
 # (LSHRS_HIP_LIBRARY: load another build of the same ABI instead - A/B measurements of compiler flags, tools/ab_build.py)
@@ -188,6 +188,26 @@ def _declare(lib: ctypes.CDLL) -> None:
     # (cand_ids, scores, pair_off, ucount, keep, out_off, q, max_candidates, out_ids, out_scores, done_host, epoch, stream)
     lib.lshrs_query_rank_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
     lib.lshrs_query_rank_f32.restype = c.c_int
+    # the id -> row table of a device-resident vector store (csrc/idmap.hip)
+    lib.lshrs_idmap_bytes.argtypes = [i64]
+    lib.lshrs_idmap_bytes.restype = i64
+    lib.lshrs_idmap_home_slot.argtypes = [i64, i64]
+    lib.lshrs_idmap_home_slot.restype = i64
+    # (table, slots, ids, n, first_row, report, stream)
+    lib.lshrs_idmap_insert_i64.argtypes = [vp, i64, vp, i64, i64, vp, vp]
+    lib.lshrs_idmap_insert_i64.restype = c.c_int
+    # (table, slots, ids, n, live_count, stream)
+    lib.lshrs_idmap_erase_i64.argtypes = [vp, i64, vp, i64, vp, vp]
+    lib.lshrs_idmap_erase_i64.restype = c.c_int
+    # (table, slots, ids, n, rows, err, stream)
+    lib.lshrs_idmap_lookup_i64.argtypes = [vp, i64, vp, i64, vp, vp, vp]
+    lib.lshrs_idmap_lookup_i64.restype = c.c_int
+    # (table, slots, cand_ids, pair_off, ucount, q, total, rows, err, stream)
+    lib.lshrs_idmap_lookup_ragged_i64.argtypes = [vp, i64, vp, vp, vp, i32, i64, vp, vp, vp]
+    lib.lshrs_idmap_lookup_ragged_i64.restype = c.c_int
+    # (src, src_slots, dst, dst_slots, report, stream)
+    lib.lshrs_idmap_rehash.argtypes = [vp, i64, vp, i64, vp, vp]
+    lib.lshrs_idmap_rehash.restype = c.c_int
     lib.lshrs_pipe_create.argtypes = [i32, i32, i32, i32, i32]
     lib.lshrs_pipe_create.restype = vp
     lib.lshrs_pipe_destroy.argtypes = [vp]
@@ -241,6 +261,13 @@ EXPORTS = (
     "lshrs_quantize_rows_i8",
     "lshrs_quantize_rows_f8e4m3",
     "lshrs_query_rank_f32",
+    "lshrs_idmap_bytes",
+    "lshrs_idmap_home_slot",
+    "lshrs_idmap_insert_i64",
+    "lshrs_idmap_erase_i64",
+    "lshrs_idmap_lookup_i64",
+    "lshrs_idmap_lookup_ragged_i64",
+    "lshrs_idmap_rehash",
     "lshrs_pipe_create",
     "lshrs_pipe_destroy",
     "lshrs_pipe_hash_f32",

@@ -26,6 +26,7 @@ import numpy as np
 from . import _native
 from .similarity import _upload as upload
 from .similarity import corpus_entry
+from .vectors import NO_VECTOR_MSG
 from .windows import _U
 
 __all__ = ["DeviceBuckets", "TooLarge", "candidates_from_index", "candidates_from_pairs", "rank_and_cut"]
@@ -243,12 +244,13 @@ def candidates_from_pairs(members: np.ndarray, bands: np.ndarray, pair_off: np.n
 
 
 def rank_and_cut(lists: _Lists, top_k: Optional[int], top_p: Optional[float], *, queries_dev=None, corpus=None,
-                 cand_rows=None) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
+                 cand_rows=None, idmap=None) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
     """The ranked, cut answer of every query as arrays ``(ids, scores or None, bounds)``: query i's ids are
     ``ids[bounds[i]:bounds[i + 1]]``.  ``top_p`` None: the collision order, first ``top_k`` (lshrs/core/main.py:619-625).
     Else the candidates scored against ``corpus`` (device (m, dim) float32, bfloat16, float16, int8 or float8_e4m3fn -
-    ``similarity.corpus_entry``; row = ``cand_rows`` entry, default the id itself), ordered by score, cut to
-    ``max(1, ceil(n * top_p))`` and ``top_k`` (:646-657)."""
+    ``similarity.corpus_entry``; row = ``cand_rows`` entry, default the id itself - or, with ``idmap`` = (table, slots) of a
+    ``DeviceVectors``, the row its id -> row table names: ``lshrs_idmap_lookup_ragged_i64``, one launch in front of the
+    rerank), ordered by score, cut to ``max(1, ceil(n * top_p))`` and ``top_k`` (:646-657)."""
     torch = _native.require_gpu()
     lib = _native.load()
     dev, nq = lists.dev, lists.nq
@@ -265,6 +267,12 @@ def rank_and_cut(lists: _Lists, top_k: Optional[int], top_p: Optional[float], *,
             rows = lists.cand_ids if cand_rows is None else cand_rows
             scores = torch.empty(max(1, lists.total), dtype=torch.float32, device=dev)
             err = torch.zeros(1, dtype=torch.int32, device=dev)
+            if idmap is not None and cand_rows is None:
+                rows = torch.empty_like(lists.cand_ids)
+                _native.check(lib.lshrs_idmap_lookup_ragged_i64(idmap[0].data_ptr(), int(idmap[1]), lists.cand_ids.data_ptr(),
+                                                                lists.pair_off.data_ptr(), lists.ucount.data_ptr(), nq,
+                                                                lists.total, rows.data_ptr(), err.data_ptr(), stream),
+                              "lshrs_idmap_lookup_ragged_i64")
             _native.check(getattr(lib, entry)(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)),
                                               int(corpus.shape[1]), queries_dev.data_ptr(), nq, rows.data_ptr(),
                                               lists.pair_off.data_ptr(), lists.ucount.data_ptr(), lists.total,
@@ -301,6 +309,8 @@ def rank_and_cut(lists: _Lists, top_k: Optional[int], top_p: Optional[float], *,
             code = int(err.item())
             if code & 5:
                 raise ValueError("Cannot normalize zero vector")
+            if code & 256:
+                raise IndexError(NO_VECTOR_MSG)
             if code & 2:
                 raise IndexError("candidate index out of range of the corpus")
             return host[:8 * kept].view(np.int64), host[8 * kept:].view(np.float32), bounds
@@ -348,6 +358,7 @@ class OneQuery:
             self.cand_ids = torch.empty(self.CAP, dtype=torch.int64, device=dev)
             self.scores = torch.empty(self.CAP, dtype=torch.float32, device=dev)
             self.slots = None
+            self.rows_dev = None               # the candidates' rows in a DeviceVectors (allocated when one is attached)
         self.epoch = 0
         p32 = self.pin_i32.data_ptr()
         self.ptr = dict(x=self.pin_x.data_ptr(), keys=self.keys_dev.data_ptr(), flags=self.pin_flags.data_ptr(),
@@ -364,9 +375,10 @@ class OneQuery:
                 and hasher.dim % 4 == 0 and 8 <= hasher.dim <= 4096 and hasher.rows_per_band != 1
                 and hasher._replay_model() in (1, 2))
 
-    def run(self, hasher, vec: np.ndarray, desc, nseg: int, max_id: int, top_k: int, top_p: float, corpus):
+    def run(self, hasher, vec: np.ndarray, desc, nseg: int, max_id: int, top_k: int, top_p: float, corpus, idmap=None):
         """(number of candidates or -1, ids int64[keep], scores float32[keep] or None, row flag).  ``top_k`` -1 = all,
-        ``top_p`` -1.0 = no rerank."""
+        ``top_p`` -1.0 = no rerank.  ``idmap``: (table, slots) of the ``DeviceVectors`` whose row block ``corpus`` is - the
+        candidates' ids are translated to its rows by one more launch of the chain."""
         torch = _native.require_gpu()
         lib = _native.load()
         nb, bb, dim = self.shape
@@ -397,9 +409,16 @@ class OneQuery:
                                               float(top_p), 1 if rerank else 0, p["pair_off"], p["cand"], p["ucount"], p["keep"],
                                               p["out_off"], p["ids"], p["done"], epoch, p["x"] if rerank else None,
                                               p["x_dev"] if rerank else None, dim if rerank else 0, raw)
+            cand_rows = p["cand"]
+            if rerank and idmap is not None and not rc:
+                if self.rows_dev is None:
+                    self.rows_dev = torch.empty(self.CAP, dtype=torch.int64, device=dev)
+                cand_rows = self.rows_dev.data_ptr()
+                rc = lib.lshrs_idmap_lookup_ragged_i64(idmap[0].data_ptr(), int(idmap[1]), p["cand"], p["pair_off"], p["ucount"],
+                                                       1, 4096, cand_rows, p["err"], raw)
             if rerank and not rc:
                 rc = getattr(lib, entry)(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)), dim, p["x_dev"], 1,
-                                         p["cand"], p["pair_off"], p["ucount"], 4096, p["scores"], p["err"], raw)
+                                         cand_rows, p["pair_off"], p["ucount"], 4096, p["scores"], p["err"], raw)
                 rc = rc or lib.lshrs_query_rank_f32(p["cand"], p["scores"], p["pair_off"], p["ucount"], p["keep"], p["zero_off"], 1,
                                                     self.CAP, p["ids"], p["scores_out"], p["done"], epoch, raw)
             if rc:
@@ -417,6 +436,8 @@ class OneQuery:
         if rerank and ucount > 0 and not (flag & 1):
             if err & 5:
                 raise ValueError("Cannot normalize zero vector")
+            if err & 256:
+                raise IndexError(NO_VECTOR_MSG)
             if err & 2:
                 raise IndexError("candidate index out of range of the corpus")
         return ucount, ids, scores, flag

@@ -41,6 +41,7 @@ from .similarity import corpus_entry
 from .similarity import rerank_padded_arrays as _rerank_padded
 from .similarity import top_k_cosine
 from .storage import BucketOperation, default_storage
+from .vectors import NO_VECTOR_MSG, DeviceVectors
 
 logger = logging.getLogger(__name__)
 
@@ -128,6 +129,15 @@ class LSHRS:
     ``reference_blas``: which BLAS build the band keys are the reference's keys on (``LSHHasher``; "host" = this process's
     NumPy).  A named build is stored by ``save_to_disk`` (key ``lshrs_amd`` of metadata.json, which the reference's loader
     does not read) and by pickle, so an index and everything that queries it hash alike on any machine.
+    ``keep_vectors``: ``None`` (default: the index keeps no vectors, as the reference), the name of a dtype ("float32",
+    "bfloat16", "float16", "int8", "float8_e4m3fn": the index creates a :class:`DeviceVectors` on the hasher's first
+    device) or a ``DeviceVectors`` to use.  ``index`` / ``ingest`` / ``create_signatures`` then also put every vector whose
+    buckets they hand to the storage into that store under its id (``idx.vectors``), ``delete`` / ``clear`` take them out,
+    and - while no other corpus is attached - queries rerank against it on the device: ``vector_fetch_fn`` is never called
+    for a rerank.  Vectors that live on the GPU are copied / converted where they are; a host array given to ``index()`` is
+    uploaded a second time for the store (the streamed chunk's device buffer is released before the buckets are handed
+    over).  The store's dtype travels with ``save_to_disk`` / pickle (a restored index has an empty
+    store of the same kind); the vectors themselves through ``DeviceVectors.save`` / ``load``.
     """
 
     def __init__(
@@ -154,6 +164,7 @@ class LSHRS:
         packed_ingest: Union[bool, str] = "auto",
         devices: Optional[Sequence[int]] = None,
         reference_blas: str = "host",
+        keep_vectors: Union[None, str, DeviceVectors] = None,
     ) -> None:
         if dim <= 0:
             raise ValueError("Vector dimensionality must be greater than zero")
@@ -189,6 +200,14 @@ class LSHRS:
         self._buffer: List[BucketOperation] = []
         self._buffer_lock = Lock()
         self._corpus = None                  # device-resident vectors for the rerank (set_corpus)
+        if keep_vectors is None or isinstance(keep_vectors, DeviceVectors):
+            self._vectors = keep_vectors
+        elif isinstance(keep_vectors, str):
+            self._vectors = DeviceVectors(dim, keep_vectors, device=getattr(self._hasher, "_device", None))
+        else:
+            raise ValueError("keep_vectors must be None, the name of a dtype or a DeviceVectors")
+        if self._vectors is not None and self._vectors.dim != dim:
+            raise ValueError(f"keep_vectors holds vectors of dimension {self._vectors.dim}; the index has {dim}")
         self.last_query_stats: Dict[str, Any] = {}
         from ._query_device import DeviceBuckets
 
@@ -265,6 +284,7 @@ class LSHRS:
         if flag & 1:
             raise ValueError(_ZERO_MSG)
         self._enqueue_packed(int(index), keys)
+        self._keep(np.array([int(index)], dtype=np.int64), arr.reshape(1, -1))
         self._flush_buffer_if_needed()
 
     def index(self, indices: Sequence[int], vectors: Optional[np.ndarray] = None) -> None:
@@ -291,6 +311,7 @@ class LSHRS:
                     for lo in range(0, arr.shape[0], self.lane_rows):
                         ingest.submit(id_arr[lo:lo + self.lane_rows], arr[lo:lo + self.lane_rows])
             return
+        rows_given = arr                    # (what the vector store takes: a tensor on the GPU stays there)
         if resident:                        # (a store that does not take arrays gets the host form of the same rows)
             arr = np.asarray(arr.detach().cpu().numpy(), dtype=np.float32)
         sink = self._packed_sink(n_ops)
@@ -326,6 +347,7 @@ class LSHRS:
                 for lo in range(0, stop, per_call):
                     hi = min(stop, lo + per_call)
                     sink.batch_add_packed(id_arr[lo:hi], keys[lo:hi])
+            self._keep(id_arr[:stop], rows_given[:stop])
             if error is not None:
                 raise error
             return
@@ -355,6 +377,7 @@ class LSHRS:
             if full:
                 self.flush()
             j += take
+        self._keep(ids[:stop], rows_given[:stop])
         if error is not None:
             raise error
         self.flush()
@@ -400,12 +423,15 @@ class LSHRS:
             return candidate_indices[:top_k]
 
         qh.check_cut(None, top_p)
-        if self._corpus is not None:
-            # the indexed vectors are resident on the device (set_corpus): gathered and scored there, nothing fetched
+        corpus = self._rerank_corpus()
+        if corpus is not None:
+            # the indexed vectors are resident on the device (set_corpus / keep_vectors): gathered and scored there, nothing fetched
             from .similarity import rerank_batch
 
-            ranked = rerank_batch(query_vector[None], self._corpus, np.asarray([candidate_indices], dtype=np.int64),
-                                  k=len(candidate_indices))[0]
+            cand = np.asarray([candidate_indices], dtype=np.int64)
+            if isinstance(corpus, DeviceVectors):
+                corpus, cand = self._stored_rows(corpus, cand)
+            ranked = rerank_batch(query_vector[None], corpus, cand, k=len(candidate_indices))[0]
         else:
             arr = qh.fetch_checked(self._require_vector_fetch_fn(), self._dim, candidate_indices)
             ranked = top_k_cosine(query_vector, arr, k=len(candidate_indices))
@@ -429,7 +455,10 @@ class LSHRS:
             return None
         bad_p = top_p is not None and not 0 < top_p <= 1
         rerank = top_p is not None and not bad_p
-        corpus = self._corpus
+        corpus, idmap = self._rerank_corpus(), None
+        if rerank and isinstance(corpus, DeviceVectors):
+            # the index's own vectors, under their ids: one more launch in the chain translates the candidates to rows
+            corpus, *idmap = corpus.snapshot()
         if rerank:
             try:
                 corpus_entry(corpus, "ragged", self._dim)       # a device corpus the rerank reads as it is (f32 / 16 / 8 bits)
@@ -444,14 +473,15 @@ class LSHRS:
             if one is None or one.shape != (h.num_bands, h.band_bytes, h.dim):
                 one = self._one_query[dev.index] = qd.OneQuery(h, dev)
             k_arg = top_k if (top_k is not None and top_k > 0) else -1
-            ucount, ids, scores, flag = one.run(h, query_vector, *table, k_arg, float(top_p) if rerank else -1.0, corpus)
+            ucount, ids, scores, flag = one.run(h, query_vector, *table, k_arg, float(top_p) if rerank else -1.0, corpus,
+                                                idmap=idmap)
             if flag & 1:
                 raise ValueError(_ZERO_MSG)
             if ucount < 0:
                 # more pairs than the chain's fixed capacity: the batch form, which sizes its arrays by what it finds (and takes
                 # lists beyond the LDS network through global memory)
                 ids, scores, _ = self._query_many_device(query_vector[None], top_k if (top_k is None or top_k > 0) else None,
-                                                         top_p if rerank else None, corpus if rerank else None)
+                                                         top_p if rerank else None, self._rerank_corpus() if rerank else None)
                 ucount = len(ids)
         except qd.TooLarge:
             return None
@@ -475,10 +505,44 @@ class LSHRS:
         them on the host).  16- and 8-bit rows are converted to float32 exactly inside the rerank: the scores are those of
         ``corpus.float()`` (the reference's ``np.asarray(fetch(ids), dtype=np.float32)``), at half / a quarter of the memory
         and of the bytes gathered.  ``lshrs_amd.quantize_rows`` makes the 8-bit rows (a scale per row, which a cosine does
-        not see).  ``None`` detaches."""
-        if corpus is not None and (getattr(corpus, "ndim", 0) != 2 or int(corpus.shape[1]) != self._dim):
+        not see).  Or a :class:`DeviceVectors`: the vectors under the ids they were added with, whatever those are - the
+        candidates' ids are translated to its rows on the device.  ``None`` detaches (an index built with ``keep_vectors``
+        then reranks against its own store again)."""
+        if isinstance(corpus, DeviceVectors):
+            if corpus.dim != self._dim:
+                raise ValueError(f"corpus must hold vectors of dimension {self._dim}")
+        elif corpus is not None and (getattr(corpus, "ndim", 0) != 2 or int(corpus.shape[1]) != self._dim):
             raise ValueError(f"corpus must have shape (m, {self._dim})")
         self._corpus = corpus
+
+    @property
+    def vectors(self) -> Optional[DeviceVectors]:
+        """The store ``keep_vectors`` asked for (None without it)."""
+        return self._vectors
+
+    def _rerank_corpus(self):
+        """What queries rerank against on the device: the attached corpus, else the index's own vectors, else None."""
+        return self._corpus if self._corpus is not None else self._vectors
+
+    def _keep(self, ids, rows) -> None:
+        """``keep_vectors``: rows whose buckets went to the storage, into the store under their ids."""
+        if self._vectors is not None and len(ids):
+            self._vectors.add(ids, rows)
+
+    @staticmethod
+    def _stored_rows(store: DeviceVectors, cand: np.ndarray):
+        """(row block, rows of the candidate ids ``cand`` as a device tensor) - padding (-1) stays -1; an id without a stored
+        vector raises."""
+        from . import _native
+
+        torch = _native.require_gpu()
+        rows, _, _ = store.snapshot()
+        with torch.cuda.device(rows.device):
+            ids_dev = torch.from_numpy(np.ascontiguousarray(cand, dtype=np.int64)).to(rows.device)
+            cand_rows, _ = store.translate(ids_dev)
+            if bool(((cand_rows < 0) & (ids_dev >= 0)).any()):
+                raise IndexError(NO_VECTOR_MSG)
+        return rows, cand_rows
 
     def query_many(self, vectors, *, top_k: Optional[int] = 10, top_p: Optional[float] = None, corpus=None,
                    return_arrays: bool = False, engine: str = "auto"):
@@ -493,7 +557,7 @@ class LSHRS:
         ``corpus``: optional device-resident ``(m, dim)`` float32, bfloat16, float16, int8 or float8_e4m3fn tensor whose row
         ``i`` is the vector of id ``i`` (default: what :meth:`set_corpus` attached); with it the candidates are gathered on
         the device and ``vector_fetch_fn`` is not called (16- and 8-bit rows are converted to float32 exactly: the scores of
-        ``corpus.float()``; another dtype raises ``ValueError``).
+        ``corpus.float()``; another dtype raises ``ValueError``) - or a :class:`DeviceVectors` (see :meth:`set_corpus`).
         ``return_arrays``: ``(ids, scores, bounds)`` instead of lists - query ``i``'s answer is ``ids[bounds[i]:bounds[i + 1]]``
         (int64) with ``scores[...]`` (float32; ``None`` without ``top_p``): no Python object per result.
         ``engine``: "auto" (the device path wherever the hasher is the HIP one; a batch with a candidate list beyond the
@@ -509,7 +573,9 @@ class LSHRS:
         if engine not in ("auto", "device", "host"):
             raise ValueError("engine must be 'auto', 'device' or 'host'")
         if corpus is None:
-            corpus = self._corpus
+            corpus = self._rerank_corpus()
+        elif isinstance(corpus, DeviceVectors) and corpus.dim != self._dim:
+            raise ValueError(f"corpus must hold vectors of dimension {self._dim}")
         if int(arr.shape[0]) == 0:
             empty = (np.empty(0, np.int64), None if top_p is None else np.empty(0, np.float32), np.zeros(1, np.int64))
             return empty if return_arrays else []
@@ -544,6 +610,9 @@ class LSHRS:
 
         torch = _native.require_gpu()
         nq = int(arr.shape[0])
+        idmap = None
+        if isinstance(corpus, DeviceVectors) and top_p is not None:
+            corpus, *idmap = corpus.snapshot()
         if _device_tensor(corpus) is not None:
             dev = corpus.device
         elif isinstance(arr, torch.Tensor):
@@ -565,7 +634,8 @@ class LSHRS:
             if lists.total == 0:
                 return np.empty(0, np.int64), np.empty(0, np.float32), np.zeros(nq + 1, np.int64)
             if corpus is not None:
-                return qd.rank_and_cut(lists, top_k, top_p, queries_dev=x, corpus=qd.corpus_on(corpus, dev, self._dim))
+                return qd.rank_and_cut(lists, top_k, top_p, queries_dev=x, corpus=qd.corpus_on(corpus, dev, self._dim),
+                                       idmap=idmap)
             # no resident corpus: the candidates' vectors come from the caller's fetch function, list by list as the reference
             # asks for them (main.py:629), and travel to the device as one table; candidate j reads row `rows[j]` of it
             ucount = lists.ucount.cpu().numpy()
@@ -637,6 +707,8 @@ class LSHRS:
             table = qh.fetch_table(self._require_vector_fetch_fn(), self._dim, um, bounds)
             cand = np.full((nq, c_max), -1, dtype=np.int64)
             cand[rows, cols] = np.arange(um.shape[0], dtype=np.int64)     # row of `table` = position in the flat list
+        elif isinstance(corpus, DeviceVectors):
+            table, cand = self._stored_rows(corpus, cand_ids)
         else:
             table, cand = corpus, cand_ids
         order, scores = _rerank_padded(arr, table, cand)                   # (q, c_max): positions, descending scores
@@ -651,11 +723,15 @@ class LSHRS:
         """Remove ids from every bucket (reference: main.py:744-784)."""
         to_remove = [indices] if isinstance(indices, int) else [int(i) for i in indices]
         self._storage.remove_indices(to_remove)
+        if self._vectors is not None:
+            self._vectors.remove(to_remove)
 
     def clear(self) -> None:
         """Flush what is buffered, then drop every bucket (reference: main.py:786-796)."""
         self.flush()
         self._storage.clear()
+        if self._vectors is not None:
+            self._vectors.clear()
 
     def stats(self) -> Dict[str, Any]:
         """Static configuration summary (reference: main.py:798-840)."""
@@ -682,6 +758,8 @@ class LSHRS:
             # reference's keys ON: the named build, or - for "host" - the build this host's NumPy was recognised as, so that a
             # loader on the other kind of host can tell (`_check_recorded_blas`)
             meta["lshrs_amd"] = self._blas_record()
+            if self._vectors is not None:           # (the store's kind, not its vectors: DeviceVectors.save / load carry those)
+                meta["lshrs_amd"]["keep_vectors"] = self._vectors.dtype
             json.dump(meta, fh, indent=2)
         np.savez_compressed(out / "projections.npz", *self._hasher.projections)
 
@@ -713,7 +791,8 @@ class LSHRS:
             similarity_threshold=cfg["similarity_threshold"], buffer_size=cfg["buffer_size"],
             vector_fetch_fn=vector_fetch_fn, storage=storage, redis_host=redis_cfg["host"], redis_port=redis_cfg["port"],
             redis_db=redis_cfg["db"], redis_password=redis_cfg["password"], redis_prefix=redis_cfg["prefix"],
-            decode_responses=redis_cfg["decode_responses"], seed=cfg["seed"], reference_blas=blas)
+            decode_responses=redis_cfg["decode_responses"], seed=cfg["seed"], reference_blas=blas,
+            keep_vectors=extra.get("keep_vectors"))
         with np.load(src / "projections.npz") as data:
             inst._hasher.projections = [data[f"arr_{i}"].astype(np.float32) for i in range(len(data.files))]
         return inst
@@ -730,6 +809,7 @@ class LSHRS:
         state["lshrs_amd"] = {
             "host_blas": self._blas_record().get("host_blas"),
             "packed_ingest": self._packed_ingest,
+            "keep_vectors": self._vectors.dtype if self._vectors is not None else None,
             "device": getattr(h, "_device", None) if isinstance(getattr(h, "_device", None), (int, str, type(None))) else str(h._device),
             "hasher_kwargs": {**{k: getattr(h, k) for k in ("tie_break", "precision", "tie_replay", "margin_guard",
                                                             "tie_threads", "audit_every", "audit_unflagged",
@@ -759,7 +839,8 @@ class LSHRS:
             similarity_threshold=cfg["similarity_threshold"], buffer_size=cfg["buffer_size"], vector_fetch_fn=None,
             redis_host=rc["host"], redis_port=rc["port"], redis_db=rc["db"], redis_password=rc["password"],
             redis_prefix=rc["prefix"], decode_responses=rc["decode_responses"], seed=cfg["seed"], hasher=hasher,
-            packed_ingest=extra.get("packed_ingest", "auto"), storage=_DeferredStorage(rc))
+            packed_ingest=extra.get("packed_ingest", "auto"), storage=_DeferredStorage(rc),
+            keep_vectors=extra.get("keep_vectors"))
         self.__dict__ = restored.__dict__
         self._hasher.projections = [np.asarray(m, dtype=np.float32) for m in state["projections"]]
 
@@ -835,7 +916,8 @@ class LSHRS:
         from ._ingest import CsrIngest
 
         return CsrIngest(self._ingest_hashers(), self._packed_sink(1 << 62), lambda: ValueError(_ZERO_MSG),
-                         lambda: ValueError("index must be non-negative"), inline=inline)
+                         lambda: ValueError("index must be non-negative"), inline=inline,
+                         on_stored=self._keep if self._vectors is not None else None)
 
     def _check_rows(self, indices, vectors):
         """The rows of one batch - float32; a torch tensor that lives on a GPU stays where it is - with the reference's shape

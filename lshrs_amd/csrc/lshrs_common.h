@@ -434,6 +434,25 @@ constexpr int res_wave_floats(int rt) { return 32 * rt + 144 * rt + 3 * kResList
 template <int NCT, int KT>
 constexpr int res_lds_floats() { return KT * NCT * 512 + 512 + 256 + 512 + res_waves(NCT, KT) * res_wave_floats(res_rt(NCT, KT)); }
 
+// ------------------------------------------------------------------------------------------
+// id -> row table (idmap.hip)
+// ------------------------------------------------------------------------------------------
+// Home slot of an id in a table of `slots` (a power of two) slots: the low bits of murmur3's 64-bit finalizer, every bit of
+// which depends on every bit of the id - dense ids, ids that are multiples of a power of two or of `slots` itself all
+// spread.  The kernels and lshrs_idmap_home_slot (host, tests) call this one function.
+__host__ __device__ inline uint64_t idmap_mix(uint64_t x) {
+  x ^= x >> 33;
+  x *= 0xff51afd7ed558ccdULL;
+  x ^= x >> 33;
+  x *= 0xc4ceb9fe1a85ec53ULL;
+  x ^= x >> 33;
+  return x;
+}
+__host__ __device__ inline int64_t idmap_home(int64_t id, int64_t slots) {
+  return (int64_t)(idmap_mix((uint64_t)id) & (uint64_t)(slots - 1));
+}
+inline bool idmap_slots_ok(int64_t slots) { return slots > 0 && (slots & (slots - 1)) == 0; }
+
 struct Opts {            // the caller's lshrs_sig_opts, or all-null
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   unsigned long long* clock_probe = nullptr;
