@@ -421,7 +421,9 @@ int lshrs_l2_normalize_f32(const float* X, int64_t n, int64_t ldx, int32_t dim, 
 /* Per-query descending order — replaces argpartition + argsort (similarity.py:174-179).
  *   scores (q, c) f32 -> order (q, k) int32 positions, sorted (q, k) f32, k <= c.
  * Ties are broken by ascending position (the reference's order on ties is unspecified);
- * NaN scores sort last.  c <= 16384: one LDS-resident bitonic network per query, workspace may be NULL.
+ * NaN scores sort last, by position among themselves.  The two zeros are NOT a tie: +0.0 ranks
+ * ahead of -0.0 wherever they stand (the key is the sign-magnitude order of the bits; a cosine
+ * computed here never comes out -0.0).  c <= 16384: one LDS-resident bitonic network per query, workspace may be NULL.
  * Longer lists run the same network over `workspace` (lshrs_topk_workspace_bytes(q, c) bytes, 8-byte
  * aligned) in global memory; q <= 65535 there. */
 int64_t lshrs_topk_workspace_bytes(int32_t q, int32_t c);
@@ -475,8 +477,8 @@ int lshrs_query_scan_i32(const int32_t* counts, int32_t q, int32_t top_k, double
 
 /* Collision counts and candidate order, one workgroup per query, in LDS.  pair_off int64[q + 1]: the scan of pair_count;
  * max_pairs >= every list (<= LSHRS_QUERY_MAX_PAIRS).  Query qi's candidates - distinct ids over its buckets - are written
- * to cand_ids[pair_off[qi] .. + ucount[qi]) ordered by (-collisions, id) (ucount[qi] = -1: the list is longer than max_pairs -
- * nothing written), cand_hits (optional) the collisions of each: an id
+ * to cand_ids[pair_off[qi] .. + ucount[qi]) ordered by (-collisions, id) (ucount[qi] = -1: the list is longer than max_pairs - exactly
+ * that number, not the power of two the network is sized for - nothing written), cand_hits (optional) the collisions of each: an id
  * found twice in ONE band's bucket (two segments) counts once there (buckets are sets).  Needs every id < 2^(63 - bits(num_bands)).
  * _index: members read from the segments through lshrs_query_lookup_u8's slots; _pairs: (member, band) pairs handed in flat
  * (query qi's at pair_off[qi]) - for stores that only answer get_bucket (lshrs/storage/redis.py:282). */
@@ -501,8 +503,9 @@ int lshrs_query_collide_big_i64(const lshrs_bucket_segment* segments, int32_t ns
 /* ONE query in ONE launch (behind lshrs_sig_hash_small_replay_f32, whose keys may sit in pinned host memory): lookup, pair
  * list, collision count and order, and the cut of lshrs_query_scan_i32 (top_k < 0 / top_p < 0: none) by a single workgroup -
  * LSHRS.get_top_k / get_above_p, the reference's calling pattern (lshrs/core/main.py:524-658), without a size read back in
- * between.  slot_*: scratch for num_bands * nseg slots; max_pairs: what cand_ids holds (<= LSHRS_QUERY_MAX_PAIRS; a longer list
- * leaves ucount[0] = -1 and keeps nothing).  Leaves pair_off int64[2] = {0, pairs}, the ordered candidates in cand_ids,
+ * between.  slot_*: scratch for num_bands * nseg slots; max_pairs: what cand_ids holds (<= LSHRS_QUERY_MAX_PAIRS; a list of more
+ * than max_pairs pairs (that number itself, not the power of two the network is sized for) leaves ucount[0] = -1, keep[0] = 0, pair_off[1] = 0, and cand_ids / out_ids untouched).
+ * Leaves pair_off int64[2] = {0, pairs}, the ordered candidates in cand_ids,
  * ucount[0], keep[0], out_off int64[3] = {0, keep, ucount} (each DEVICE or PINNED HOST memory; out_off is what a host that
  * polls done_host reads: the launches behind this one take the other three from device memory).  rerank_follows == 0: the first keep ids
  * go to out_ids and `epoch` to *done_host (optional) behind them; != 0: lshrs_cosine_ragged_f32 and lshrs_query_rank_f32 (q = 1,
@@ -569,10 +572,12 @@ int lshrs_quantize_rows_i8(const float* X, int64_t n, int64_t ldx, int32_t dim, 
 int lshrs_quantize_rows_f8e4m3(const float* X, int64_t n, int64_t ldx, int32_t dim, uint8_t* out, int64_t ldo,
                                uint8_t* status, void* stream);
 
-/* Per query the first keep[qi] candidates in descending score (ties: ascending position in the list; NaN last - the order of
- * lshrs_topk_desc_f32) into the compact arrays out_ids / out_scores at out_off[qi]; lists and scores at pair_off[qi], ucount[qi]
- * long; a list longer than max_candidates (<= LSHRS_QUERY_MAX_PAIRS: the LDS network) is left to the caller (lshrs_topk_desc_f32
- * ranks it through global memory).  scores == NULL: the order the lists already have (out_scores unused; any length).
+/* Per query the first keep[qi] candidates in descending score (ties: ascending position in the list; NaN last, by position;
+ * +0.0 ahead of -0.0 wherever they stand - the order of lshrs_topk_desc_f32) into the compact arrays out_ids / out_scores at
+ * out_off[qi]; lists and scores at pair_off[qi], ucount[qi]
+ * long; a list longer than max_candidates (exactly that number, <= LSHRS_QUERY_MAX_PAIRS: the LDS network is sized for it) is left
+ * to the caller - nothing of it is written (lshrs_topk_desc_f32 ranks it through global memory).  keep[qi] = 0: nothing written.
+ * scores == NULL: the order the lists already have (out_scores unused; any length).
  * done_host (optional, q == 1 only; PINNED HOST int32[1]): ONE query - LSHRS.get_top_k / get_above_p, the reference's own calling
  * pattern - whose sizes the host never reads back in between (fixed capacities: max_pairs / max_candidates = what the buffers
  * hold; a list beyond them leaves ucount = -1) and whose out_ids / out_scores / offsets may be pinned host memory themselves:

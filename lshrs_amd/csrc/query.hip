@@ -373,8 +373,8 @@ __global__ __launch_bounds__(kQThreads) void query_collide_kernel(const Segment*
   const int qi = blockIdx.x;
   const int64_t base = pair_off[qi];
   const int64_t L64 = pair_off[qi + 1] - base;
-  if (L64 <= 0 || L64 > max_items) {      // nothing to count - or more than the LDS network was sized for (the caller told us its
-    if (threadIdx.x == 0) ucount[qi] = L64 <= 0 ? 0 : -1;    // maximum, or a fixed capacity): -1 says so
+  if (L64 <= 0 || L64 > max_items) {      // nothing to count - or more than the caller's max_pairs (its longest list, or a fixed
+    if (threadIdx.x == 0) ucount[qi] = L64 <= 0 ? 0 : -1;    // capacity; the LDS network is sized for at least that): -1 says so
     return;
   }
   const int64_t so = (int64_t)qi * nb * nseg;
@@ -390,7 +390,7 @@ __global__ __launch_bounds__(kQThreads) void query_collide_kernel(const Segment*
 // workgroup and ONE launch behind the one-launch signature kernel: lookup, pair list, collision count and order, the cut; the
 // ids of a top-k-by-collisions answer go straight into the caller's (pinned) result array and `epoch` into *done behind them;
 // a rerank follows in two more launches (cosine_kernel over the candidates left here, query_rank_kernel, which publishes).
-// A list beyond max_items: ucount = -1, nothing kept - the host counts.
+// A list beyond max_items (the caller's max_pairs: what cand_ids holds): ucount = -1, nothing kept or written - the host counts.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kQThreads) void query_one_kernel(const uint8_t* __restrict__ keys, int nb, int bb, int bbits,
                                                               const Segment* __restrict__ segs, int nseg,
@@ -451,6 +451,7 @@ __global__ __launch_bounds__(kQThreads) void query_one_kernel(const uint8_t* __r
 // Per query: the candidates in descending score (ties by ascending candidate position, NaN last - as lshrs_topk_desc_f32),
 // the first keep[q] of them written to the caller's compact result arrays.  scores == NULL: the order the candidates
 // already have (collision order: the top_k-by-collisions answer of LSHRS.query, main.py:619-625).
+// (+0.0 ranks ahead of -0.0 wherever they stand: the key is the sign-magnitude order of the bits.)
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t desc_key(float f) {
   if (f != f) return 0xFFFFFFFFu;
@@ -563,6 +564,8 @@ int set_lds(const void* fn, size_t bytes) {
   const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   return e == hipSuccess ? 0 : -(int)e;
 }
+// LDS of the network for lists of up to max_items: a power of two.  The kernels' `max_items` is the caller's capacity itself, NOT
+// this rounded size - a list between the two would fit the network, and run over what the caller's buffers hold.
 inline size_t items_bytes(int max_items) {
   size_t p = 2 * kQThreads;          // (bitonic_sort_regs exchanges through the first 2 x kQThreads items whatever the list's length)
   while (p < (size_t)max_items) p <<= 1;
@@ -627,7 +630,7 @@ int lshrs_query_collide_index_i64(const lshrs_bucket_segment* segments, int32_t 
   if (rc) return rc;
   hipLaunchKernelGGL(query_collide_kernel<0>, dim3((unsigned)q), dim3(kQThreads), shmem, static_cast<hipStream_t>(stream),
                      reinterpret_cast<const Segment*>(segments), nseg, num_bands, collide_bits(num_bands), slot_start,
-                     slot_len, slot_off, nullptr, nullptr, pair_off, cand_ids, cand_hits, ucount, (int)(shmem / sizeof(uint64_t)));
+                     slot_len, slot_off, nullptr, nullptr, pair_off, cand_ids, cand_hits, ucount, (int)max_pairs);
   return -(int)hipGetLastError();
 }
 
@@ -643,7 +646,7 @@ int lshrs_query_collide_pairs_i64(const int64_t* members, const int32_t* bands, 
   if (rc) return rc;
   hipLaunchKernelGGL(query_collide_kernel<1>, dim3((unsigned)q), dim3(kQThreads), shmem, static_cast<hipStream_t>(stream),
                      nullptr, 0, num_bands, collide_bits(num_bands), nullptr, nullptr, nullptr, members, bands, pair_off,
-                     cand_ids, cand_hits, ucount, (int)(shmem / sizeof(uint64_t)));
+                     cand_ids, cand_hits, ucount, (int)max_pairs);
   return -(int)hipGetLastError();
 }
 
@@ -709,7 +712,7 @@ int lshrs_query_one_u8(const uint8_t* keys, int32_t num_bands, int32_t band_byte
   if (rc) return rc;
   hipLaunchKernelGGL(query_one_kernel, dim3(1), dim3(kQThreads), shmem, static_cast<hipStream_t>(stream), keys, num_bands,
                      band_bytes, collide_bits(num_bands), reinterpret_cast<const Segment*>(segments), nseg, slot_start, slot_len,
-                     slot_off, (int)(shmem / sizeof(uint64_t)), top_k, top_p, rerank_follows ? 0 : 1, pair_off, cand_ids, ucount,
+                     slot_off, (int)max_pairs, top_k, top_p, rerank_follows ? 0 : 1, pair_off, cand_ids, ucount,
                      keep, out_off, out_ids, done, (int)epoch, copy_src, copy_dst, (int)copy_n);
   return -(int)hipGetLastError();
 }
@@ -735,7 +738,7 @@ int lshrs_query_rank_f32(const int64_t* cand_ids, const float* scores, const int
   if (rc) return rc;
   hipLaunchKernelGGL(query_rank_kernel, dim3((unsigned)q), dim3(kQThreads), shmem, static_cast<hipStream_t>(stream),
                      cand_ids, scores, pair_off, ucount, keep, out_off, out_ids, out_scores, done, (int)epoch,
-                     (int)(shmem / sizeof(uint64_t)));
+                     (int)max_candidates);
   return -(int)hipGetLastError();
 }
 

@@ -10,6 +10,8 @@ import math
 import numpy as np
 import pytest
 
+from tests._ranking import judge_ranking
+
 pytestmark = pytest.mark.gpu
 HALF = ("bfloat16", "float16")
 
@@ -19,17 +21,6 @@ def _torch():
 
     assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
     return torch
-
-
-def _same_ranking(got, want, tol=1e-5, gap=2e-5):
-    """(copy of tests/test_gpu_query_device.py's helper) Lists of (id, score): equal lengths; scores within `tol` wherever
-    the ids agree; where they do not, the two are near-ties of the reference."""
-    assert len(got) == len(want)
-    for j, ((gi, gs), (wi, ws)) in enumerate(zip(got, want)):
-        if gi == wi:
-            assert abs(gs - ws) <= tol, (j, gi, gs, ws)
-        else:
-            assert abs(gs - ws) <= tol + gap, (j, gi, wi, gs, ws)
 
 
 def _clustered(rng, n, dim, clusters, spread):
@@ -162,8 +153,9 @@ def test_query_many_on_a_half_corpus_equals_the_reference_flow(dim, num_perm, nb
                 listed = idx.query_many(queries, top_k=top_k, top_p=top_p, corpus=corpus, engine="device")
                 hosted = idx.query_many(queries[sample], top_k=top_k, top_p=top_p, corpus=corpus, engine="host")
                 for j, i in enumerate(sample):
-                    _same_ranking(listed[i], want[j])
-                    _same_ranking(hosted[j], want[j])
+                    judged = dict(query=queries[i], candidates=lit_all[i], fetch=fetch)
+                    judge_ranking(listed[i], want[j], **judged)
+                    judge_ranking(hosted[j], want[j], **judged)
                 for i in range(nq):
                     n_cand = len(lit_all[i])
                     lim = 0 if n_cand == 0 else max(1, math.ceil(n_cand * top_p))
@@ -208,8 +200,9 @@ def test_one_query_reranks_a_bf16_corpus_in_its_chain(monkeypatch):
     idx.set_corpus(corpus)
     P = idx._hasher.projections
     for v in queries:
-        _same_ranking(idx.get_above_p(v, p=0.5), O.query_literal(store, P, 768, v, top_k=None, top_p=0.5, fetch=fetch))
-        _same_ranking(idx.query(v, top_k=3, top_p=1.0), O.query_literal(store, P, 768, v, top_k=3, top_p=1.0, fetch=fetch))
+        judged = dict(query=v, candidates=O.query_literal(store, P, 768, v, top_k=None), fetch=fetch)
+        judge_ranking(idx.get_above_p(v, p=0.5), O.query_literal(store, P, 768, v, top_k=None, top_p=0.5, fetch=fetch), **judged)
+        judge_ranking(idx.query(v, top_k=3, top_p=1.0), O.query_literal(store, P, 768, v, top_k=3, top_p=1.0, fetch=fetch), **judged)
     assert idx._one_query, "the single-query chain was not taken"
 
 

@@ -10,26 +10,10 @@ import math
 import numpy as np
 import pytest
 
+from tests._ranking import judge_ranking
+from tests._ranking import literal_lists as _literal_lists
+
 pytestmark = pytest.mark.gpu
-
-
-def _literal_lists(segments, keys, nb, bb):
-    """Per query: [(id, collisions)] ordered by (-collisions, id) - dict counting over the buckets the keys select, an id
-    once per band however many segments list it there."""
-    out = []
-    for qi in range(keys.shape[0]):
-        counts = {}
-        for b in range(nb):
-            code = (b << (8 * bb)) | int.from_bytes(keys[qi, b].tobytes(), "little")
-            members = set()
-            for seg in segments:
-                g = int(np.searchsorted(seg.codes, code))
-                if g < len(seg) and int(seg.codes[g]) == code:
-                    members.update(seg.members[seg.offsets[g]:seg.offsets[g + 1]].tolist())
-            for m in members:
-                counts[m] = counts.get(m, 0) + 1
-        out.append(sorted(counts.items(), key=lambda kv: (-kv[1], kv[0])))
-    return out
 
 
 def _random_segments(rng, nb, bb, nseg, n_rows, key_space, id_hi):
@@ -170,18 +154,6 @@ def _clustered(rng, n, dim, clusters, spread):
     return (np.repeat(centers, n // clusters, axis=0) + spread * rng.standard_normal((n, dim))).astype(np.float32)
 
 
-def _same_ranking(got, want, tol=1e-5, gap=2e-5):
-    """Lists of (id, score): equal lengths; scores within `tol` wherever the ids agree; where they do not, the two are
-    near-ties of the reference - scores at most `gap` apart (the reference's own order among ties is unspecified, and a tie
-    may straddle the cut: the partner is then not in the list at all)."""
-    assert len(got) == len(want)
-    for j, ((gi, gs), (wi, ws)) in enumerate(zip(got, want)):
-        if gi == wi:
-            assert abs(gs - ws) <= tol, (j, gi, gs, ws)
-        else:
-            assert abs(gs - ws) <= tol + gap, (j, gi, wi, gs, ws)
-
-
 @pytest.mark.parametrize("dim,num_perm,nb,r,n,clusters,spread", [
     (64, 64, 16, 4, 3000, 300, 0.35),          # one-byte keys, 16 crowded buckets per band: lists of thousands, many equal counts
     (768, 256, 16, 16, 4000, 400, 0.3),        # config 2's shape
@@ -239,9 +211,10 @@ def test_query_many_on_the_device_equals_the_reference_flow(dim, num_perm, nb, r
         fetched = idx.query_many(queries[sample], top_k=top_k, top_p=top_p, engine="device")
         hosted = idx.query_many(queries[sample], top_k=top_k, top_p=top_p, corpus=corpus, engine="host")
         for j, i in enumerate(sample):
-            _same_ranking(on_corpus[i], want[j])
-            _same_ranking(fetched[j], want[j])
-            _same_ranking(hosted[j], want[j])
+            judged = dict(query=queries[i], candidates=lit_all[i], fetch=fetch)
+            judge_ranking(on_corpus[i], want[j], **judged)
+            judge_ranking(fetched[j], want[j], **judged)
+            judge_ranking(hosted[j], want[j], **judged)
             n_cand = len(lit_all[i])
             lim = 0 if n_cand == 0 else max(1, math.ceil(n_cand * top_p))
             assert len(on_corpus[i]) == (min(lim, top_k) if top_k is not None else lim)
@@ -252,8 +225,9 @@ def test_query_many_on_the_device_equals_the_reference_flow(dim, num_perm, nb, r
     # one query at a time: the reference's own entry points on the attached corpus
     idx.set_corpus(corpus)
     for i in sample[:40]:
-        _same_ranking(idx.get_above_p(queries[i], p=0.5),
-                      O.query_literal(store, P, dim, queries[i], top_k=None, top_p=0.5, fetch=fetch))
+        judge_ranking(idx.get_above_p(queries[i], p=0.5),
+                      O.query_literal(store, P, dim, queries[i], top_k=None, top_p=0.5, fetch=fetch),
+                      query=queries[i], candidates=lit_all[i], fetch=fetch)
         assert idx.get_top_k(queries[i], topk=4) == lit_all[i][:4]
     # deleting ids replaces segments: the mirror follows
     gone = [int(w[0]) for w in lit_all[:200] if w]
@@ -317,15 +291,26 @@ def test_stores_with_get_bucket_only_count_on_the_device_too():
         table = corpus if not isinstance(store, InMemoryStorage) else torch.cat([corpus, corpus[:500]])
         full = np.concatenate([data, data[:500]])
         got = idx.query_many(queries[:60], top_k=None, top_p=0.5, corpus=table, engine="device")
-        for g, q in zip(got, queries[:60]):
-            _same_ranking(g, O.query_literal(store, P, dim, q, top_k=None, top_p=0.5, fetch=lambda ids: full[np.asarray(ids)]))
+        fetch_full = lambda ids: full[np.asarray(ids)]  # noqa: E731
+        for g, q, cands in zip(got, queries[:60], want):
+            judge_ranking(g, O.query_literal(store, P, dim, q, top_k=None, top_p=0.5, fetch=fetch_full),
+                          query=q, candidates=cands, fetch=fetch_full)
 
 
 def test_lists_beyond_the_lds_network_go_through_global_memory():
     """A query whose buckets hold more than LSHRS_QUERY_MAX_PAIRS members (here 24 000 and 320 000 pairs; 1 500 and 20 000 distinct
     candidates - the second also beyond the rank kernel's network): gathered, sorted, counted and ordered through global memory
     (`lshrs_query_collide_big_i64`: K3's long-list network), ranked by `lshrs_topk_desc_f32` - the literal flow's answers, in one
-    batch with ordinary queries, through `query_many` and through `get_top_k` / `get_above_p`."""
+    batch with ordinary queries, through `query_many` and through `get_top_k` / `get_above_p`.
+
+    The near-copies cannot be told apart by score (1e-4 noise: `gap=1e-4` for the judge's position-by-position check, and for
+    that check only), so a second, spread-out group is indexed beside them - 3 000 clustered rows at spread 0.3 - with one query
+    inside it.  With n = 20 000 that query shares a bucket with the copies in one band or more: its pair list is beyond the LDS
+    network and its 20 000 + candidates beyond the rank kernel's, so the ids the global-memory path re-pairs with their scores
+    are ids that CAN be told apart (about 2 000 of the group among them).  With n = 1 500 such a list cannot be reached with 64
+    projections: the group itself gives a query about 3 300 pairs, so nine of the sixteen bands would have to be shared with
+    the copies.  There the group's query is an ordinary list in one batch with the long ones, and the global-memory path is
+    left to the n = 20 000 round (tests/test_gpu_rank_kernels.py feeds the kernels themselves)."""
     import torch
 
     from lshrs_amd import LSHRS, InMemoryStorage, _native
@@ -337,31 +322,46 @@ def test_lists_beyond_the_lds_network_go_through_global_memory():
     dim = 32
     base = rng.standard_normal(dim).astype(np.float32)
     other = rng.standard_normal((300, dim)).astype(np.float32)
+    group_rng = np.random.default_rng(10)
+    group = _clustered(group_rng, 3000, dim, 100, 0.3)
+    inside = (group[:50] + 0.05 * group_rng.standard_normal((50, dim))).astype(np.float32)
     for n in (1500, 20_000):
         near = (base[None, :] + 1e-4 * rng.standard_normal((n, dim))).astype(np.float32)
-        data = np.concatenate([near, other])
+        data = np.concatenate([near, other, group])
         store = InMemoryStorage()
         idx = LSHRS(dim=dim, num_perm=64, storage=store, packed_ingest=True)
         idx.index(np.arange(n), near)
         idx.index(np.arange(n, n + 300), other)
+        idx.index(np.arange(n + 300, n + 3300), group)
         idx.index(np.arange(50), near[:50])                               # ids indexed twice: once per bucket
         P = idx._hasher.projections
-        q = np.stack([base, -base, other[3] + 0.01, base * 2.0, other[7]]).astype(np.float32)
+        # the group's query: the first whose buckets hold more members, summed over the bands, than the LDS network takes pairs (else
+        # the first); an id in several bands counts once per band, so this is the pair list but for ids indexed twice
+        members = lambda v: sum(len(store.get_bucket(b, h)) for b, h in enumerate(O.hash_vector_literal(P, v, dim)))  # noqa: E731
+        long_ones = [v for v in inside if members(v) > 16384]
+        assert long_ones or n == 1500
+        q = np.stack([base, -base, other[3] + 0.01, base * 2.0, other[7], long_ones[0] if long_ones else inside[0]]).astype(np.float32)
         want = [O.query_literal(store, P, dim, v, top_k=7) for v in q]
         assert len(want[0]) == 7 and idx.query_many(q, top_k=7, engine="device") == want
         assert idx.last_query_stats["longest_list"] == 16384 and idx.last_query_stats["pairs"] >= 2 * 16 * n
-        assert idx.query_many(q, top_k=None, engine="device") == [O.query_literal(store, P, dim, v, top_k=None) for v in q]
+        cands = [O.query_literal(store, P, dim, v, top_k=None) for v in q]
+        assert idx.query_many(q, top_k=None, engine="device") == cands
+        told_apart = sum(1 for i in cands[5] if i >= n + 300)
+        assert told_apart > 100 and (n == 1500 or len(cands[5]) > 16384 + told_apart), (told_apart, len(cands[5]))
         assert idx.query_many(q, top_k=7, engine="host") == want
         corpus = torch.from_numpy(data).cuda()
         fetch = lambda ids: data[np.asarray(ids)]  # noqa: E731
         for top_k, top_p in ((None, 0.002), (5, 1.0), (None, 1.0)):
             got = idx.query_many(q, top_k=top_k, top_p=top_p, corpus=corpus, engine="device")
-            for g, v in zip(got, q):
-                _same_ranking(g, O.query_literal(store, P, dim, v, top_k=top_k, top_p=top_p, fetch=fetch), gap=1e-4)
+            for g, v, c in zip(got, q, cands):
+                judge_ranking(g, O.query_literal(store, P, dim, v, top_k=top_k, top_p=top_p, fetch=fetch), query=v, candidates=c,
+                              fetch=fetch, gap=1e-4)
         # one query per call: the chain says "beyond my capacity", the batch form answers
         assert idx.get_top_k(base, topk=7) == want[0] and idx.get_top_k(-base, topk=7) == want[1]
         idx.set_corpus(corpus)
-        _same_ranking(idx.get_above_p(base, p=0.002), O.query_literal(store, P, dim, base, top_k=None, top_p=0.002, fetch=fetch), gap=1e-4)
+        for v, c in ((base, cands[0]), (q[5], cands[5])):
+            judge_ranking(idx.get_above_p(v, p=0.002), O.query_literal(store, P, dim, v, top_k=None, top_p=0.002, fetch=fetch),
+                          query=v, candidates=c, fetch=fetch, gap=1e-4)
     # pairs handed over by the host (a store with get_bucket only) are not taken beyond the LDS network: the host counts
     with pytest.raises(qd.TooLarge):
         qd.candidates_from_pairs(np.zeros(20_000, np.int64), np.zeros(20_000, np.int32), np.array([0, 20_000], np.int64), 16,
@@ -431,8 +431,10 @@ def test_one_query_is_one_chain_of_launches_and_equals_the_reference_flow():
     # rerank on the attached corpus
     idx.set_corpus(torch.from_numpy(data).cuda())
     for q in queries[:120]:
+        cands = O.query_literal(store, P, dim, q, top_k=None)
         for kw in ({"top_k": None, "top_p": 0.5}, {"top_k": 3, "top_p": 1.0}, {"top_k": None, "top_p": 0.01}):
-            _same_ranking(idx.query(q, **kw), O.query_literal(store, P, dim, q, fetch=fetch, **kw))
+            judge_ranking(idx.query(q, **kw), O.query_literal(store, P, dim, q, fetch=fetch, **kw), query=q, candidates=cands,
+                          fetch=fetch)
     res = idx.get_above_p(queries[1], p=0.5)
     assert all(type(i) is int and type(s) is float for i, s in res)
     # errors, in the reference's order: a zero vector first; the arguments only when there are candidates
@@ -461,7 +463,9 @@ def test_one_query_is_one_chain_of_launches_and_equals_the_reference_flow():
     plain = LSHRS(dim=dim, num_perm=256, storage=InMemoryStorage(), packed_ingest=False, vector_fetch_fn=fetch)
     plain.index(np.arange(600), data[:600])
     assert plain.get_top_k(data[5] + 0.01, topk=3) == O.query_literal(plain._storage, P, dim, data[5] + 0.01, top_k=3)
-    _same_ranking(plain.get_above_p(data[5] + 0.01, p=0.5), O.query_literal(plain._storage, P, dim, data[5] + 0.01, top_k=None, top_p=0.5, fetch=fetch))
+    judge_ranking(plain.get_above_p(data[5] + 0.01, p=0.5),
+                  O.query_literal(plain._storage, P, dim, data[5] + 0.01, top_k=None, top_p=0.5, fetch=fetch), query=data[5] + 0.01,
+                  candidates=O.query_literal(plain._storage, P, dim, data[5] + 0.01, top_k=None), fetch=fetch)
     assert not plain._one_query and len(calls) == n_calls
 
 

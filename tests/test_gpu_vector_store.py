@@ -9,6 +9,8 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from tests._ranking import judge_ranking
+
 pytestmark = pytest.mark.gpu
 DTYPES = ("float32", "bfloat16", "float16", "int8", "float8_e4m3fn")
 
@@ -18,17 +20,6 @@ def _torch():
 
     assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
     return torch
-
-
-def _same_ranking(got, want, tol=1e-5, gap=2e-5):
-    """(copy of tests/test_gpu_query_device.py's helper) Lists of (id, score): equal lengths; scores within `tol` wherever
-    the ids agree; where they do not, the two are near-ties of the reference."""
-    assert len(got) == len(want)
-    for j, ((gi, gs), (wi, ws)) in enumerate(zip(got, want)):
-        if gi == wi:
-            assert abs(gs - ws) <= tol, (j, gi, gs, ws)
-        else:
-            assert abs(gs - ws) <= tol + gap, (j, gi, wi, gs, ws)
 
 
 def _clustered(rng, n, dim, clusters, spread):
@@ -342,6 +333,7 @@ def test_the_reference_flow_is_the_judge(dim, num_perm, nb, r, n, clusters, spre
         queries = (data[rng.choice(n, nq, replace=False)] + 0.05 * rng.standard_normal((nq, dim))).astype(np.float32)
         queries[::16] = rng.standard_normal((len(queries[::16]), dim)).astype(np.float32)
         P = idx._hasher.projections
+        cands = [O.query_literal(store, P, dim, v, top_k=None) for v in queries]
         for top_k, top_p in ((None, 0.5), (3, 1.0), (5, 0.01)):
             want = [O.query_literal(store, P, dim, v, top_k=top_k, top_p=top_p, fetch=latest.fetch) for v in queries]
             assert sum(len(w) for w in want) > nq // 2
@@ -349,13 +341,15 @@ def test_the_reference_flow_is_the_judge(dim, num_perm, nb, r, n, clusters, spre
             hosted = idx.query_many(queries, top_k=top_k, top_p=top_p, engine="host")
             a_ids, a_scores, a_bounds = idx.query_many(queries, top_k=top_k, top_p=top_p, return_arrays=True)
             for i in range(nq):                                  # every query
-                _same_ranking(listed[i], want[i])
-                _same_ranking(hosted[i], want[i])
+                judged = dict(query=queries[i], candidates=cands[i], fetch=latest.fetch)
+                judge_ranking(listed[i], want[i], **judged)
+                judge_ranking(hosted[i], want[i], **judged)
                 arr = list(zip(a_ids[a_bounds[i]:a_bounds[i + 1]].tolist(), a_scores[a_bounds[i]:a_bounds[i + 1]].astype(np.float64).tolist()))
                 assert arr == listed[i]
-        for v in queries:
-            _same_ranking(idx.get_above_p(v, p=0.5), O.query_literal(store, P, dim, v, top_k=None, top_p=0.5, fetch=latest.fetch))
-            _same_ranking(idx.query(v, top_k=3, top_p=1.0), O.query_literal(store, P, dim, v, top_k=3, top_p=1.0, fetch=latest.fetch))
+        for v, c in zip(queries, cands):
+            judged = dict(query=v, candidates=c, fetch=latest.fetch)
+            judge_ranking(idx.get_above_p(v, p=0.5), O.query_literal(store, P, dim, v, top_k=None, top_p=0.5, fetch=latest.fetch), **judged)
+            judge_ranking(idx.query(v, top_k=3, top_p=1.0), O.query_literal(store, P, dim, v, top_k=3, top_p=1.0, fetch=latest.fetch), **judged)
 
 
 @pytest.mark.parametrize("name", ("bfloat16", "int8"))
@@ -387,8 +381,9 @@ def test_one_query_stays_one_chain(monkeypatch, name):
     monkeypatch.setattr(core, "top_k_cosine", boom)
     P = idx._hasher.projections
     for v in queries:
-        _same_ranking(idx.get_above_p(v, p=0.5), O.query_literal(store, P, dim, v, top_k=None, top_p=0.5, fetch=latest.fetch))
-        _same_ranking(idx.query(v, top_k=3, top_p=1.0), O.query_literal(store, P, dim, v, top_k=3, top_p=1.0, fetch=latest.fetch))
+        judged = dict(query=v, candidates=O.query_literal(store, P, dim, v, top_k=None), fetch=latest.fetch)
+        judge_ranking(idx.get_above_p(v, p=0.5), O.query_literal(store, P, dim, v, top_k=None, top_p=0.5, fetch=latest.fetch), **judged)
+        judge_ranking(idx.query(v, top_k=3, top_p=1.0), O.query_literal(store, P, dim, v, top_k=3, top_p=1.0, fetch=latest.fetch), **judged)
     assert idx._one_query, "the single-query chain was not taken"
 
 
@@ -556,8 +551,9 @@ def test_a_candidate_without_a_stored_vector():
     fetch = lambda want: data[np.searchsorted(big_ids, np.asarray(want))]  # noqa: E731
     assert sum(len(g) for g in got) > 0
     for i, v in enumerate(q):
-        _same_ranking(got[i], O.query_literal(big._storage, P, dim, v, top_k=None, top_p=0.5, fetch=fetch))
-        _same_ranking(big.get_above_p(v, p=0.5), O.query_literal(big._storage, P, dim, v, top_k=None, top_p=0.5, fetch=fetch))
+        judged = dict(query=v, candidates=O.query_literal(big._storage, P, dim, v, top_k=None), fetch=fetch)
+        judge_ranking(got[i], O.query_literal(big._storage, P, dim, v, top_k=None, top_p=0.5, fetch=fetch), **judged)
+        judge_ranking(big.get_above_p(v, p=0.5), O.query_literal(big._storage, P, dim, v, top_k=None, top_p=0.5, fetch=fetch), **judged)
 
 
 # ------------------------------------------------------------------------------------------ persistence
