@@ -39,7 +39,8 @@ int lshrs_abi_version(void);
  * WRONG KEYS BY DESIGN and must never be mistaken for the product: bit LSHRS_BUILD_WRONG_KEYS says so, and
  * lshrs_amd/_native.py refuses to load such a build unless LSHRS_ALLOW_AB=1 is set.  LSHRS_BUILD_TUNED: switches and
  * constants that change speed only (the keys stay the reference's).  Bits 8 and up name the individual switches
- * (csrc/sig16.hip, sig16r.hip, sig_replay.hip: lshrs_flags_*).  The product build returns 0. */
+ * (csrc/sig16.hip, sig16r.hip, sig_replay.hip: lshrs_flags_*).  The product build returns 0 - unless the process runs with
+ * LSHRS_SIG16_HALF_MAX_TILES set (the run-time measurement switch of stage 1's workgroup shape): LSHRS_BUILD_TUNED and bit 25. */
 #define LSHRS_BUILD_WRONG_KEYS 0x1u
 #define LSHRS_BUILD_TUNED      0x2u
 uint32_t lshrs_build_flags(void);

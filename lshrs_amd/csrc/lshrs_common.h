@@ -285,6 +285,15 @@ __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// A raw buffer descriptor (stride 0, `bytes` records) whose words are wave-uniform TO THE COMPILER: readfirstlane on the inputs,
+// or hipcc wraps every buffer instruction that takes it in a waterfall loop (v_readfirstlane x 4, compare, s_and_saveexec).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_buffer(const void* base, unsigned bytes) {
+  const uint64_t a = reinterpret_cast<uint64_t>(base);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0,
+                                           (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+
 // Ballot + deposit in one block.  The 64-lane compare result (VCC: low half = the 32 columns of row rho,
 // high half = the same columns of row rho + 4) is written into the two lanes that own those output
 // words with v_writelane_b32 (immediate lane select; this clang exposes no builtin for it).

@@ -92,10 +92,9 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
   // l = (r = l>>3, q = l&7) fetches 16-byte chunk q ^ r ^ (j&1) of row 8j + r, so an 8-lane group covers one whole
   // line (in permuted order) and the read-back (each lane: its row's two chunks of the k-tile quarter it feeds) is
   // conflict-free for ds_read_b128's 16-lane groups.
-  unsigned poff[kPP], xfo[2 * RT], xrd[RT][2];
-#pragma unroll
-  for (int q = 0; q < kPP; ++q) poff[q] = (unsigned)(((W * (W == 8 ? q : 0) + wave) * 64 + lane) * 16);
-  // (W = 4: one offset in a register, piece d is W d KiB behind it on both sides - four would not fit beside the accumulators)
+  // (fragments: one lane offset in a register, piece d is W d KiB behind it on both sides - the scalar offset of the piece carries it)
+  unsigned xfo[2 * RT], xrd[2];
+  const unsigned poff = (unsigned)((wave * 64 + lane) * 16);
   {
     const int r8 = lane >> 3, q8 = lane & 7;
 #pragma unroll
@@ -104,11 +103,10 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
       const int64_t rl = (r < args.n ? r : args.n - 1) - blk_row0;   // clamp: loads stay in bounds, stores are masked
       xfo[j] = (unsigned)((rl * args.ldx + 4 * (q8 ^ r8 ^ (j & 1))) * 4);
     }
+    {
+      const int j = r16 >> 3, r = r16 & 7;       // this lane's row of row tile 0: chunks 2g, 2g+1; row tile rt is 2048 rt bytes behind
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      const int R = 16 * rt + r16, j = R >> 3, r = R & 7;       // this lane's row of row tile rt: chunks 2g, 2g+1
-#pragma unroll
-      for (int c = 0; c < 2; ++c) xrd[rt][c] = (unsigned)(j * 1024 + (r * 8 + ((2 * g + c) ^ r ^ (j & 1))) * 16);
+      for (int c = 0; c < 2; ++c) xrd[c] = (unsigned)(wave * (kXWave * 4) + j * 1024 + (r * 8 + ((2 * g + c) ^ r ^ (j & 1))) * 16);
     }
   }
 
@@ -133,51 +131,66 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
     t_real = __builtin_amdgcn_s_memrealtime();
   }
 
-  struct Dma { const char* pg; const char* xg; float* pdst; float* xdst; int j0; };
   const int last_valid_chunks = PARTIAL ? (args.dim - (ktiles - 1) * kKTile) / 4 : 8;   // WHOLE 16-byte chunks of a row in the last k-tile
   const int rem = PARTIAL ? (args.dim & 3) : 0;                                          // elements of the chunk behind them
   const int tail_off = PARTIAL ? (args.dim - 4 - (ktiles - 1) * kKTile) * 4 : 0;         // the row's last four elements, from the last k-tile's start (bytes)
-  auto plan = [&](int s) {          // what stage s issues: fragments of stage s+2, x pieces 4(s&1).. of tile (s>>1)+2
-    Dma f;
-    const int ns = s + 2, c = ns < lasts ? ns : lasts;
-    const int nt = (s >> 1) + 2, t = nt < ktiles ? nt : ktiles - 1;
-    f.pg = img + (size_t)c * 16384;
-    f.xg = xblk + (size_t)t * (kKTile * 4);
-    f.pdst = lds + (ns % 3) * kPHalf + wave * kFragFloats;
-    f.j0 = kXPS * (s & 1);
-    f.xdst = lds + 3 * kPHalf + (nt % kXDepth) * kXTile + wave * kXWave + f.j0 * kFragFloats;
-    return f;
+  // The LDS-DMA goes through two buffer descriptors, built once from wave-uniform values: a piece is then
+  // `buffer_load_dwordx4 v_lane_offset, s[descriptor], s_uniform_offset offen lds` - the lane offsets stay the 32-bit values
+  // they are, the stage / k-tile advance is a scalar, and no vector instruction forms an address per piece (the global form
+  // costs one 64-bit vector add per piece and a 64-bit register pair per lane offset).  The fragment image of this column
+  // block; x: exactly what this workgroup may touch (the row clamp above is the mechanism, the range check returns zeros
+  // and is only the net under it; < 2^31: 256 rows of < 2^20 elements).  Rows at any 4-byte address go through it like
+  // aligned ones.  PARTIAL keeps the global form for its x pieces (the chunk redirection below is as it was); its
+  // fragments take the descriptor.
+  const int rows_here = (int)(args.n - blk_row0 < (int64_t)kRows ? args.n - blk_row0 : (int64_t)kRows);
+  const __amdgpu_buffer_rsrc_t rs_img = uniform_buffer(img, (unsigned)ktiles * 32768u);
+  const __amdgpu_buffer_rsrc_t rs_x = uniform_buffer(xblk, (unsigned)(((int64_t)(rows_here - 1) * args.ldx + args.dim) * 4));
+  LDS_AS char* const lds_b = (LDS_AS char*)lds;
+  // Ring positions are counters that rotate in scalar registers (no `% 3` of the stage number): the LDS byte offsets of the
+  // fragment slots of stages s, s + 1, s + 2 and of the x slots of k-tiles t, t + 1, t + 2 (two-deep x ring: t + 2 is t's)
+  unsigned fr0 = 0u, fr1 = (unsigned)kPHalf * 4u, fr2 = 2u * (unsigned)kPHalf * 4u;
+  unsigned xq0 = 3u * kPHalf * 4u, xq1 = xq0 + (unsigned)kXTile * 4u, xq2 = kXDepth == 3 ? xq1 + (unsigned)kXTile * 4u : xq0;
+  const unsigned wave_f = (unsigned)wave * (kFragFloats * 4u), wave_x = (unsigned)wave * (kXWave * 4u);
+  // fragment piece d of stage c (clamped by the caller) into the slot at LDS byte `slot`
+  auto issue_frag = [&](int d, int c, unsigned slot) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_img, (LDS_AS void*)(lds_b + (slot + wave_f + (unsigned)(W * d * 1024))), 16, (int)poff,
+                                             c * 16384 + W * d * 1024, 0, 0);
   };
-  auto issue = [&](const Dma& f, int d) {
+  // x piece j (0 .. 2 RT - 1) of k-tile t (clamped by the caller) into the x slot at LDS byte `slot`
+  auto issue_x = [&](int j, int t, unsigned slot) {
+    LDS_AS void* dst = (LDS_AS void*)(lds_b + (slot + wave_x + (unsigned)(j * 1024)));
     if constexpr (!PARTIAL) {
-      if (d < kPP)
-        __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(f.pg + (W == 8 ? poff[d] : poff[0] + (unsigned)(W * d * 1024))),
-                                         (LDS_AS void*)(f.pdst + W * d * kFragFloats), 16, 0, 0);
-      else
-        __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(f.xg + (f.j0 ? xfo[kXPS + d - kPP] : xfo[d - kPP])),
-                                         (LDS_AS void*)(f.xdst + (d - kPP) * kFragFloats), 16, 0, LSHRS_X_AUX);
-    } else if (d < kPP) {
-      __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(f.pg + (W == 8 ? poff[d] : poff[0] + (unsigned)(W * d * 1024))),
-                                       (LDS_AS void*)(f.pdst + W * d * kFragFloats), 16, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, dst, 16, (int)xfo[j], t * (kKTile * 4), 0, LSHRS_X_AUX);
     } else {
       // branch-free (a branch here changes where hipcc joins the accumulator tiles around the inline-asm MFMAs): in the last
       // k-tile a chunk that is not wholly inside the row is fetched from the row's last four elements instead; this lane's
       // chunk of the line, as in xfo
-      const unsigned off = f.j0 ? xfo[kXPS + d - kPP] : xfo[d - kPP];
-      const int lim = f.xg == xblk + (size_t)(ktiles - 1) * (kKTile * 4) ? last_valid_chunks : 8;
-      const int chunk = (int)((lane & 7) ^ (lane >> 3) ^ ((f.j0 + d - kPP) & 1));
+      const unsigned off = xfo[j];
+      const int lim = t == ktiles - 1 ? last_valid_chunks : 8;
+      const int chunk = (int)((lane & 7) ^ (lane >> 3) ^ (j & 1));
       const int o2 = chunk >= lim ? (int)off - 16 * chunk + tail_off : (int)off;      // (off < 2^30: 256 rows of < 2^20 elements)
-      __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(f.xg + o2),
-                                       (LDS_AS void*)(f.xdst + (d - kPP) * kFragFloats), 16, 0, LSHRS_X_AUX);
+      __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(xblk + (size_t)t * (kKTile * 4) + o2), dst, 16, 0, LSHRS_X_AUX);
+    }
+  };
+  // what stage s issues: fragments of stage s + 2, x pieces kXPS (s & 1) .. of tile (s >> 1) + 2; piece d of the kPP + kXPS
+  auto issue = [&](int s, int ch, int d) {
+    if (d < kPP) {
+      const int ns = s + 2;
+      issue_frag(d, ns < lasts ? ns : lasts, fr2);
+    } else {
+      const int nt = (s >> 1) + 2;
+      issue_x(kXPS * ch + d - kPP, nt < ktiles ? nt : ktiles - 1, xq2);
     }
   };
   f32x4 xr[RT][2];                           // raw f32 x of one k-tile: [row tile][chunk]
-  auto read_x = [&](int t) {
-    const char* xt = reinterpret_cast<const char*>(lds + 3 * kPHalf + (t % kXDepth) * kXTile + wave * kXWave);
+  auto read_x = [&](int t, unsigned slot) {   // k-tile t from the x slot at LDS byte `slot`: two vector adds, row tile 1 is an immediate
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
+    for (int c = 0; c < 2; ++c) {
+      unsigned at = xrd[c] + slot;
+      asm volatile("" : "+v"(at));            // (opaque: hipcc otherwise keeps an address register per read and ring position)
 #pragma unroll
-      for (int c = 0; c < 2; ++c) xr[rt][c] = *reinterpret_cast<const f32x4*>(xt + xrd[rt][c]);
+      for (int rt = 0; rt < RT; ++rt) xr[rt][c] = *reinterpret_cast<const LDS_AS f32x4*>(lds_b + (at + 2048u * rt));
+    }
     if constexpr (PARTIAL) {                // chunks 2 g, 2 g + 1 of the last k-tile: past the row's end they read as zero (selects, no branch)
       const int lim = t >= ktiles - 1 ? last_valid_chunks : 8;
 #pragma unroll
@@ -201,13 +214,18 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
   auto split_step = [&](int q, Bf16Pairs (&hi)[RT], Bf16Pairs (&mid)[RT]) {   // slice q (0..kSlices-1) of one k-tile's split
     const int pair = q / 3, step = q % 3, rt = pair >> 2, pr = pair & 3, c = pr >> 1, e = 2 * (pr & 1);
     const float v0 = xr[rt][c][e], v1 = xr[rt][c][e + 1];
+    // ONE conversion per pair, as an asm statement (the instruction hipcc selects for the cast; left to it, in four pairs of
+    // a k-tile it converts the two elements separately and packs them again)
     if (step == 0) {
-      const bf16x2 hp = bf16x2{(__bf16)v0, (__bf16)v1};
+      bf16x2 hp;
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hp) : "v"(v0), "v"(v1));
       hi[rt].p[pr] = hp;
       r0 = v0 - (float)hp[0];
       r1 = v1 - (float)hp[1];
     } else if (step == 1) {
-      mid[rt].p[pr] = bf16x2{(__bf16)r0, (__bf16)r1};
+      bf16x2 mp;
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(mp) : "v"(r0), "v"(r1));
+      mid[rt].p[pr] = mp;
     } else {
       ss[rt] = __builtin_amdgcn_fdot2_f32_bf16(hi[rt].p[pr], hi[rt].p[pr], ss[rt], false);
 #ifndef LSHRS_AB_NO_XMID_NORM          // (A/B builds only, tools/ab_build.py: what ||x_mid||^2 costs stage 1; keys are wrong without it)
@@ -219,13 +237,15 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
   // Fragments travel in EIGHTHS of a stage: 2 column tiles x {hi, mid} = 4 ds_read_b128 = 16 VGPRs, two buffers.
   // (Quarters, as in sig_kernel, push this kernel over 256 VGPRs next to its 256 accumulator AGPRs: hipcc then
   // shuffles accumulators through v_accvgpr moves inside the loop.)
-  auto read_eighth = [&](const float* base, int e, f32x4 (&f)[2][2]) {
+  // `base`: this lane's address in the stage's slot (ONE vector add per stage), the eighths are immediate offsets
+  auto read_eighth = [&](unsigned base, int e, f32x4 (&f)[2][2]) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      f[j][0] = *reinterpret_cast<const f32x4*>(base + (((2 * e + j) * 2 + 0) * 64 + lane) * 4);
-      f[j][1] = *reinterpret_cast<const f32x4*>(base + (((2 * e + j) * 2 + 1) * 64 + lane) * 4);
+      f[j][0] = *reinterpret_cast<const LDS_AS f32x4*>(lds_b + (base + (unsigned)(((2 * e + j) * 2 + 0) * 1024)));
+      f[j][1] = *reinterpret_cast<const LDS_AS f32x4*>(lds_b + (base + (unsigned)(((2 * e + j) * 2 + 1) * 1024)));
     }
   };
+  const unsigned lane16 = (unsigned)lane * 16u;
   // MFMA k (0..11) of an eighth: term k / 4 of xh*ph + xh*pm + xm*ph, column tile ct0 + (k / 2) % 2, row tile k % 2: the
   // four accumulator tiles of the eighth take turns, so two MFMAs on the same tile are four instructions (64 cycles)
   // apart.  (Two apart - tile order (j, term, rt) - the result of a 4-pass MFMA is not back in time and hipcc pads every
@@ -260,7 +280,8 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
   auto stage = [&](int s, const int ch, const bool first, const Bf16Pairs (&hc)[RT], const Bf16Pairs (&mc)[RT],
                    const Bf16Pairs (&hp)[RT], const Bf16Pairs (&mp)[RT], Bf16Pairs (&hn)[RT], Bf16Pairs (&mn)[RT]) {
     // hc/mc: this stage's tile; hp/mp: the tile E3(s-1) belongs to; hn/mn: where the split in flight writes
-    const float* st = lds + (s % 3) * kPHalf;
+    unsigned st = lane16 + fr0;
+    asm volatile("" : "+v"(st));
     read_eighth(st, 0, fa);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -275,7 +296,7 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
     __builtin_amdgcn_sched_barrier(0);
     wait_vmcnt<kXPS>();                                               // own fragments of stage s+1 and every older x piece
     read_eighth(st, 1, fb);
-    if (ch == 1) read_x((s >> 1) + 1);
+    if (ch == 1) read_x((s >> 1) + 1, xq1);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int k = 0; k < kE; ++k) {
@@ -286,12 +307,11 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
     __builtin_amdgcn_sched_barrier(0);
     read_eighth(st, 2, fa);
     __builtin_amdgcn_sched_barrier(0);
-    const Dma f = plan(s);
 #pragma unroll
     for (int k = 0; k < kE; ++k) {
       mfma_one(8 * ch + 2, k, fb, hc, mc);
       if (ch == 1 && k % 3 != 2) split_step((k / 3) * 2 + k % 3, hn, mn);          // first third of the next tile's split
-      if (k % kIssueStep == 0) issue(f, k / kIssueStep);
+      if (k % kIssueStep == 0) issue(s, ch, k / kIssueStep);
       __builtin_amdgcn_sched_barrier(0);
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -302,13 +322,22 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
     for (int k = 0; k < kE; ++k) {
       mfma_one(8 * ch + 4, k, fa, hc, mc);
       if (ch == 1 && k % 3 != 2) split_step(kSlices / 3 + (k / 3) * 2 + k % 3, hn, mn);   // second third
-      if (k % kIssueStep == 0) issue(f, kIssues + k / kIssueStep);
+      if (k % kIssueStep == 0) issue(s, ch, kIssues + k / kIssueStep);
       __builtin_amdgcn_sched_barrier(0);
     }
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
+    {                                       // the rings turn: a stage on, and behind a tile's second stage a k-tile on
+      const unsigned f = fr0;
+      fr0 = fr1; fr1 = fr2; fr2 = f;
+      if (ch == 1) {
+        const unsigned x = xq0;
+        xq0 = xq1;
+        if (kXDepth == 3) { xq1 = xq2; xq2 = x; } else { xq1 = x; xq2 = xq0; }
+      }
+    }
   };
   // tile t with its sets (hc, mc); the previous tile's (hp, mp) double as the target of the next tile's split
   auto tile = [&](int t, const bool first, Bf16Pairs (&hc)[RT], Bf16Pairs (&mc)[RT], Bf16Pairs (&hp)[RT], Bf16Pairs (&mp)[RT]) {
@@ -317,15 +346,15 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
   };
 
   auto issue_prologue = [&]() {     // the first two stages' fragments and the first two x tiles of the row tile entered
-    const Dma a0 = plan(-4), a1 = plan(-3), b0 = plan(-2), b1 = plan(-1);
+    const int t1 = ktiles > 1 ? 1 : 0;
 #pragma unroll
-    for (int d = 0; d < kPP; ++d) issue(b0, d);                                  // fragments of stage 0
+    for (int d = 0; d < kPP; ++d) issue_frag(d, 0, fr0);                                    // fragments of stage 0
 #pragma unroll
-    for (int d = kPP; d < kPP + kXPS; ++d) { issue(a0, d); issue(a1, d); }       // x tile 0
+    for (int d = 0; d < kXPS; ++d) { issue_x(d, 0, xq0); issue_x(kXPS + d, 0, xq0); }       // x tile 0
 #pragma unroll
-    for (int d = 0; d < kPP; ++d) issue(b1, d);                                  // fragments of stage 1
+    for (int d = 0; d < kPP; ++d) issue_frag(d, 1, fr1);                                    // fragments of stage 1
 #pragma unroll
-    for (int d = kPP; d < kPP + kXPS; ++d) { issue(b0, d); issue(b1, d); }       // x tile 1
+    for (int d = 0; d < kXPS; ++d) { issue_x(d, t1, xq1); issue_x(kXPS + d, t1, xq1); }     // x tile 1
   };
   // Static priority for the second-dispatched half of the workgroup: of the two waves of a SIMD the younger one loses the
   // VALU arbitration (priority, then age) on every stage; one s_setprio for that half, no flips (MI355X_MICROARCH.md, "Two
@@ -337,7 +366,7 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
   zero_tile_state();
   wait_vmcnt<kPP + 2 * kXPS>();
   __builtin_amdgcn_s_barrier();
-  read_x(0);
+  read_x(0, xq0);
 #pragma unroll
   for (int q = 0; q < 2 * kSlices / 3; ++q) split_step(q, hs0, ms0);   // tile 0 only: the last third rides in stage 0 as for every tile
   tile(0, true, hs0, ms0, hs1, ms1);

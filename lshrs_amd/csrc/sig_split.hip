@@ -17,7 +17,20 @@ int lshrs_abi_version(void) { return LSHRS_ABI_VERSION; }
 
 // Which measurement switches this build was compiled with (include/lshrs_hip.h, LSHRS_BUILD_*): every translation unit
 // reports its own; the product build returns 0.
-uint32_t lshrs_build_flags(void) { return lshrs_flags_sig16() | lshrs_flags_sig16r() | lshrs_flags_replay() | lshrs_flags_query(); }
+// LSHRS_SIG16_HALF_MAX_TILES (sig16_half_rows below) is no compile-time switch, but a set variable changes which workgroup
+// shape every measurement of the process is taken on: reported as LSHRS_BUILD_TUNED with bit 25.
+static int sig16_half_forced() {
+  static const int forced = [] {
+    const char* e = std::getenv("LSHRS_SIG16_HALF_MAX_TILES");
+    return e != nullptr ? std::atoi(e) : -1;
+  }();
+  return forced;
+}
+
+uint32_t lshrs_build_flags(void) {
+  return lshrs_flags_sig16() | lshrs_flags_sig16r() | lshrs_flags_replay() | lshrs_flags_query() |
+         (sig16_half_forced() >= 0 ? LSHRS_BUILD_TUNED | (1u << 25) : 0u);
+}
 
 int lshrs_stream_synchronize(void* stream) { return -(int)hipStreamSynchronize(static_cast<hipStream_t>(stream)); }
 
@@ -45,12 +58,9 @@ int lshrs_wait_done(const int32_t* done_host, int32_t epoch, int64_t spin_ns, vo
 // (measured, 1 M rows of 16 x 16: stage 1 +2 .. +5 % from 5 to 11 k-tiles, -1 .. -3 % from 12 on) and for batches whose
 // 256-row workgroups would leave half of the CUs without one (up to 32 768 rows per column block: stage 1 59 -> 47 us at 768-d).
 // LSHRS_SIG16_HALF_MAX_TILES (environment, read once; a measurement switch: tools/half_rows_ab.py) replaces both rules by a
-// k-tile limit: 0 = never, 64 = always.
+// k-tile limit: 0 = never, 64 = always; lshrs_build_flags() says when it is set.
 static bool sig16_half_rows(int ktiles, int64_t groups_of_256) {
-  static const int forced = [] {
-    const char* e = std::getenv("LSHRS_SIG16_HALF_MAX_TILES");
-    return e != nullptr ? std::atoi(e) : -1;
-  }();
+  const int forced = sig16_half_forced();
   if (forced >= 0) return ktiles <= forced;
   return ktiles <= kHalfMaxTiles || groups_of_256 <= kHalfMaxGroups;
 }
