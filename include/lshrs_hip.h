@@ -627,6 +627,45 @@ int lshrs_idmap_lookup_ragged_i64(const void* table, int64_t slots, const int64_
  * moved). */
 int lshrs_idmap_rehash(const void* src, int64_t src_slots, void* dst, int64_t dst_slots, int32_t* report, void* stream);
 
+/* ---- exhaustive scan of a device-resident row block on the matrix cores (csrc/scan.hip; lshrs_amd.exact_top_k) ----
+ * For every query the `window` rows of corpus (m, dim; row stride ldc in elements, unit inner stride, any address) with the
+ * largest APPROXIMATE cosine: rows and f32 queries enter v_mfma_f32_32x32x16_bf16 as bf16 terms (bf16, int8 and e4m3fn rows
+ * exactly, in one term; f16 and f32 rows in two; the queries in two), sums in f32, ||x||^2 summed in f32 in the same pass.
+ * row_ids (optional int64[m]): a row whose entry is negative is skipped (the superseded and erased rows of a DeviceVectors).
+ * out_rows / out_approx [q * window]: per query the rows in descending approximate score (equal scores: ascending row),
+ * padded with row -1 and -inf behind out_count[qi] = min(window, live rows).  err int32[1] (optional, zeroed by the
+ * caller): OR of 1 = a live row of zero norm (left out of every window), 4 = a query of zero norm (its window is empty) - the
+ * bits of lshrs_cosine_ragged_*.  1 <= window <= lshrs_scan_max_window() (128); dim <= 16384 and m < 2^31, else
+ * LSHRS_E_TOOLARGE.  workspace: lshrs_scan_workspace_bytes(q, m, dim, window) bytes of device memory at a 16-byte aligned
+ * address (a negative value: one of the error codes).  (Additive to ABI 7.)
+ *
+ * lshrs_scan_epsilon(elem, dim): a proven bound on |approximate score - cosine of the row as stored| for finite data whose
+ * norms and products neither overflow nor underflow f32 (DESIGN.md derives it); elem = LSHRS_SCAN_*; -1 for a bad argument.
+ * A pure host function, as lshrs_scan_workspace_bytes and lshrs_scan_max_window are. */
+#define LSHRS_SCAN_F32 0
+#define LSHRS_SCAN_BF16 1
+#define LSHRS_SCAN_F16 2
+#define LSHRS_SCAN_I8 3
+#define LSHRS_SCAN_F8E4M3 4
+int64_t lshrs_scan_workspace_bytes(int32_t q, int64_t m, int32_t dim, int32_t window);
+int32_t lshrs_scan_max_window(void);
+double lshrs_scan_epsilon(int32_t elem, int32_t dim);
+int lshrs_scan_topk_f32(const float* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, const float* queries,
+                        int32_t q, int32_t window, int64_t* out_rows, float* out_approx, int32_t* out_count, void* workspace,
+                        int32_t* err, void* stream);
+int lshrs_scan_topk_bf16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids,
+                         const float* queries, int32_t q, int32_t window, int64_t* out_rows, float* out_approx,
+                         int32_t* out_count, void* workspace, int32_t* err, void* stream);
+int lshrs_scan_topk_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids,
+                        const float* queries, int32_t q, int32_t window, int64_t* out_rows, float* out_approx,
+                        int32_t* out_count, void* workspace, int32_t* err, void* stream);
+int lshrs_scan_topk_i8(const int8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, const float* queries,
+                       int32_t q, int32_t window, int64_t* out_rows, float* out_approx, int32_t* out_count, void* workspace,
+                       int32_t* err, void* stream);
+int lshrs_scan_topk_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids,
+                           const float* queries, int32_t q, int32_t window, int64_t* out_rows, float* out_approx,
+                           int32_t* out_count, void* workspace, int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

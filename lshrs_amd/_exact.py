@@ -1,0 +1,248 @@
+"""Exact top-k cosine search over a device-resident row block - ``exact_top_k`` - and what it is made of.
+
+The ground truth an approximate index is measured against (``LSHRS.recall``) and the answer when its buckets are thin
+(``LSHRS.search_exact``, ``DeviceVectors.search``).  Two methods, the same answer:
+
+"scan"    ``lshrs_scan_topk_*`` (``csrc/scan.hip``): every row against tiles of 64 queries on the matrix cores, keeping per
+          query the ``window`` rows of the largest APPROXIMATE cosine; the window's rows are then rescored by the rerank's own
+          kernel (``lshrs_cosine_ragged_*``), so a returned score is bit for bit the rerank's score of that (query, row), and
+          ordered by ``lshrs_topk_desc_f32``.  A query is SETTLED (:func:`settled`) when the window saw every live row, or when
+          ``a_window + epsilon <= s_k``: a row left out has an approximate score of at most ``a_window``, the last one in the
+          window, hence a cosine of at most ``a_window + epsilon`` (``lshrs_scan_epsilon``: a proven bound on
+          |approximate - cosine|), which is no more than ``s_k``, the k-th rescored score.  ``exact_top_k`` passes epsilon plus
+          :func:`rerank_rounding`, so that the row's RERANK score, too, lies below ``s_k`` and both methods agree bit for bit.  Queries that are not settled - near-ties
+          across the cut, a ``k`` too large for the window - take the other method.
+"gather"  the rerank's kernels over the list of all live rows: ``lshrs_cosine_batch_*`` then ``lshrs_topk_desc_f32``, in chunks of
+          queries whose score matrix stays under 128 MiB (under 1 GiB with everything else a chunk allocates).  Every row is read once per query.
+
+No CPU compute path: the host moves arrays, decides which queries are settled from three numbers per query, and keeps counts.
+"""
+
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import numpy as np
+
+from . import _native
+from .similarity import _on_device, _raise_for_status, corpus_entry, cosine_scores_device, topk_desc_device
+
+__all__ = ["exact_top_k", "settled", "choose_window", "rerank_rounding", "scan_epsilon", "scan_max_window", "scan_windows"]
+
+METHODS = ("auto", "scan", "gather")
+# (query, live row) pairs of one chunk of the gather.  Per pair: 4 B of score, 8 B of candidate row, 1 B of status, and up to
+# 16 B of the top-k kernel's workspace (a 64-bit item, the list padded to a power of two) - 128 MiB of scores, under 1 GiB in all
+_GATHER_MAX_PAIRS = 1 << 25
+_SCAN_MAX_DIM = 16384               # what lshrs_scan_topk_* and lshrs_cosine_* take
+_SCAN_MAX_ROWS = (1 << 31) - 1
+
+
+def scan_max_window() -> int:
+    """The widest window ``lshrs_scan_topk_*`` keeps per query."""
+    return int(_native.load().lshrs_scan_max_window())
+
+
+def scan_epsilon(dtype, dim: int) -> float:
+    """``lshrs_scan_epsilon``: the proven bound on |approximate score - cosine of the stored row| for rows of ``dtype``
+    (a torch dtype or its name) and ``dim`` elements."""
+    name = str(dtype).replace("torch.", "")
+    names = {"float32": 0, "bfloat16": 1, "float16": 2, "int8": 3, "float8_e4m3fn": 4}
+    if name not in names:
+        raise ValueError(f"no scan over rows of {dtype}")
+    eps = float(_native.load().lshrs_scan_epsilon(names[name], int(dim)))
+    if eps < 0:
+        raise ValueError(f"lshrs_scan_epsilon takes 1 <= dim <= 16384; received {dim}")
+    return eps
+
+
+def rerank_rounding(dim: int) -> float:
+    """A bound on how far the rerank's float32 score of a (query, row) of ``dim`` elements can lie above the cosine.  With
+    ``u = 2^-24``: each lane of ``cosine_kernel`` sums at most ``dim / 64 + 3`` fused multiply-adds and a tree of six additions
+    joins the lanes - relative error at most ``(dim / 64 + 9) u`` of ``sum |q_i x_i| <= ||q|| ||x||`` for the dot product, half
+    that for the row's norm, half of ``(dim / 256 + 10) u`` for the query's - then two square roots, a product and a division,
+    one rounding each: ``(dim / 32 + 23) u`` to first order, charged as ``(dim / 16 + 32) u``.  The settle rule adds it to
+    epsilon, so that a row left out scores strictly below the k-th kept one in the rerank's own arithmetic, not only in exact
+    arithmetic."""
+    return (int(dim) / 16.0 + 32.0) * 2.0 ** -24
+
+
+def choose_window(k: int, max_window: int) -> int:
+    """Rows the first pass keeps per query for a top-``k`` search: the next power of two at or above ``2 k``, at most
+    ``max_window`` (``scan_max_window()``)."""
+    if int(k) <= 0:
+        raise ValueError("k must be > 0")
+    return min(int(max_window), 1 << (2 * int(k) - 1).bit_length())
+
+
+def settled(count, window: int, a_window, s_k, epsilon: float) -> np.ndarray:
+    """Which queries the first pass settled.  Per query: ``count`` rows in its window (``out_count``), ``a_window`` the last
+    approximate score of the window, ``s_k`` the k-th rescored score (``-inf`` where the window holds fewer than ``k`` rows).
+    Settled: ``count < window`` - every live row was seen - or ``a_window + epsilon <= s_k`` (evaluated in float64)."""
+    count = np.asarray(count, dtype=np.int64)
+    a = np.asarray(a_window, dtype=np.float64)
+    s = np.asarray(s_k, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        return (count < int(window)) | (a + float(epsilon) <= s)
+
+
+def _check_method(method: str) -> None:
+    if method not in METHODS:
+        raise ValueError("method must be 'auto', 'scan' or 'gather'")
+
+
+def scan_windows(corpus, queries, window: int, row_ids=None):
+    """Device-level entry of the first pass: ``corpus`` (m, dim) as ``corpus_entry`` accepts it, ``queries`` (q, dim) float32
+    contiguous on the same device, ``row_ids`` optional int64 (m,) there.  Returns ``(rows (q, window) int64, approx (q, window)
+    float32, count (q,) int32, err int32[1])`` as ``lshrs_scan_topk_*`` leaves them."""
+    torch = _native.require_gpu()
+    lib = _native.load()
+    entry = corpus_entry(corpus, "ragged").replace("lshrs_cosine_ragged_", "lshrs_scan_topk_")
+    dev = corpus.device
+    q, m, dim = int(queries.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
+    rows = torch.empty((q, window), dtype=torch.int64, device=dev)
+    approx = torch.empty((q, window), dtype=torch.float32, device=dev)
+    count = torch.empty((q,), dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    if q == 0:
+        return rows, approx, count, err
+    nbytes = int(lib.lshrs_scan_workspace_bytes(q, m, dim, window))
+    if nbytes < 0:
+        _native.check(nbytes, "lshrs_scan_workspace_bytes")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim,
+                                          row_ids.data_ptr() if row_ids is not None else None, queries.data_ptr(), q, window,
+                                          rows.data_ptr(), approx.data_ptr(), count.data_ptr(), ws.data_ptr(), err.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream), entry)
+    return rows, approx, count, err
+
+
+def _rescore(torch, lib, corpus, queries, rows, count):
+    """The rerank's score of every (query, window row): ``lshrs_cosine_ragged_*`` over the rows as they stand, ``-inf`` behind
+    each query's ``count``."""
+    entry = corpus_entry(corpus, "ragged")
+    dev = corpus.device
+    q, w = int(rows.shape[0]), int(rows.shape[1])
+    scores = torch.full((q, w), float("-inf"), dtype=torch.float32, device=dev)
+    off = torch.arange(q, dtype=torch.int64, device=dev) * w
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(getattr(lib, entry)(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)), int(corpus.shape[1]),
+                                          queries.data_ptr(), q, rows.data_ptr(), off.data_ptr(), count.data_ptr(), q * w,
+                                          scores.data_ptr(), err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), entry)
+    return scores, err
+
+
+def _gather(torch, corpus, queries, live_rows, live_ids, kk: int):
+    """Method "gather": ``(ids (q, kk), scores (q, kk))`` device tensors.  ``live_rows`` / ``live_ids``: the live rows in
+    ascending order of their ids, so that the top-k kernel's tie rule (ascending position) is ascending id.  Queries go in chunks
+    of ``_GATHER_MAX_PAIRS // live`` (at least one): what a chunk allocates - scores, the candidate matrix the batch entry wants,
+    statuses, the top-k workspace - stays under 1 GiB while ``live <= 2^25``, and grows with ``live`` beyond."""
+    q, live = int(queries.shape[0]), int(live_rows.shape[0])
+    ids = torch.empty((q, kk), dtype=torch.int64, device=corpus.device)
+    scores = torch.empty((q, kk), dtype=torch.float32, device=corpus.device)
+    step = max(1, _GATHER_MAX_PAIRS // max(live, 1))
+    for lo in range(0, q, step):
+        hi = min(q, lo + step)
+        cand = live_rows.unsqueeze(0).expand(hi - lo, live)
+        got, status, qstatus = cosine_scores_device(corpus, queries[lo:hi], cand)
+        _raise_for_status(status, qstatus)
+        order, best = topk_desc_device(got, kk)
+        ids[lo:hi] = live_ids[order.long()]
+        scores[lo:hi] = best
+    return ids, scores
+
+
+def exact_top_k(queries, corpus, k: int, *, row_ids=None, method: str = "auto", return_tensors: bool = False,
+                stats: Optional[Dict] = None):
+    """The ``k`` rows of ``corpus`` nearest to every query by cosine, exactly: ``(ids (q, kk) int64, scores (q, kk) float32)``
+    with ``kk = min(k, live rows)``, scores descending, equal scores by ascending id; NumPy arrays, or device tensors with
+    ``return_tensors``.
+
+    ``queries`` (q, dim): array-like or tensor, taken as float32.  ``corpus`` (m, dim): a device tensor of float32, bfloat16,
+    float16, int8 or float8_e4m3fn with a unit inner stride (any row stride: it is searched in place).  ``row_ids``: optional
+    int64 (m,); a row whose entry is negative does not exist for the search, the others are returned under their entry
+    (default: every row, under its index).  A score is the rerank's score of that (query, row), bit for bit.
+
+    ``method``: "scan" - one pass over the rows on the matrix cores keeps a window of candidates per query, the window is
+    rescored, and only the queries it does not settle (:func:`settled`) go through "gather"; "gather" - every query scores
+    every live row with the rerank's kernels; "auto" - "scan" while ``2 k`` fits the widest window, else "gather".  Rows of
+    more than 16 384 elements, or 2^31 rows and more, are beyond the scan and the rerank's entries alike: the call raises the
+    ``NativeLibraryError`` (``LSHRS_E_TOOLARGE``) a rerank of them raises.
+    ``stats``: a dict that receives ``queries``, ``settled_first_pass``, ``gathered``, ``window`` and ``epsilon``.
+
+    A query or a live row of zero norm raises ``ValueError("Cannot normalize zero vector")``, as the rerank does."""
+    _check_method(method)
+    if int(k) <= 0:
+        raise ValueError("k must be > 0")
+    k = int(k)
+    torch = _native.require_gpu()
+    lib = _native.load()
+    corpus_entry(corpus, "ragged")
+    dev = corpus.device
+    with torch.cuda.device(dev):
+        d_q = _on_device(torch, queries, np.float32)
+        if d_q.dim() != 2 or int(d_q.shape[1]) != int(corpus.shape[1]):
+            raise ValueError(f"queries must have shape (q, {int(corpus.shape[1])}); received {tuple(d_q.shape)}")
+        d_q = d_q.to(device=dev, dtype=torch.float32).contiguous()
+        q, m, dim = int(d_q.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
+        if dim > _SCAN_MAX_DIM or m > _SCAN_MAX_ROWS:
+            # (beyond the scan and beyond the rerank's entries alike: what a rerank of such rows raises, before any launch)
+            raise _native.NativeLibraryError(f"exact_top_k: shape outside kernel limits (LSHRS_E_TOOLARGE): {m} rows of {dim} "
+                                             f"elements; at most {_SCAN_MAX_ROWS} rows of {_SCAN_MAX_DIM}")
+        d_ids = None
+        if row_ids is not None:
+            d_ids = _on_device(torch, row_ids, np.int64).to(device=dev, dtype=torch.int64).contiguous()
+            if d_ids.dim() != 1 or int(d_ids.shape[0]) != m:
+                raise ValueError(f"row_ids must have shape ({m},); received {tuple(d_ids.shape)}")
+        live = m if d_ids is None else int((d_ids >= 0).sum())
+        kk = min(k, live)
+        max_window = int(lib.lshrs_scan_max_window())
+        use_scan = method == "scan" or (method == "auto" and 2 * k <= max_window)
+        window = choose_window(k, max_window)
+        eps = scan_epsilon(corpus.dtype, dim)
+        out = {"queries": q, "settled_first_pass": 0, "gathered": 0, "window": window if use_scan else 0, "epsilon": eps}
+        ids = torch.empty((q, kk), dtype=torch.int64, device=dev)
+        scores = torch.empty((q, kk), dtype=torch.float32, device=dev)
+        todo = None                                     # queries left to the gather: None = all of them
+        if q and kk and use_scan:
+            rows, approx, count, err = scan_windows(corpus, d_q, window, d_ids)
+            # the window in ascending order of id (padding last): the tie rule of the top-k kernel then is ascending id
+            wid = rows if d_ids is None else torch.where(rows >= 0, d_ids[rows.clamp(min=0)], rows)
+            key = torch.where(rows >= 0, wid, torch.full_like(wid, torch.iinfo(torch.int64).max))
+            by_id = torch.argsort(key, dim=1)
+            rows_s, wid = torch.gather(rows, 1, by_id).contiguous(), torch.gather(wid, 1, by_id)
+            exact, err2 = _rescore(torch, lib, corpus, d_q, rows_s, count)
+            if int(err.item()) & 5 or int(err2.item()) & 5:
+                raise ValueError("Cannot normalize zero vector")
+            kw = min(kk, window)
+            order, best = topk_desc_device(exact, kw)
+            s_k = best[:, kw - 1] if kw == kk else torch.full((q,), float("-inf"), device=dev)
+            done = settled(count.cpu().numpy(), window, approx[:, window - 1].cpu().numpy(), s_k.cpu().numpy(),
+                           eps + rerank_rounding(dim))
+            ids[:, :kw] = torch.gather(wid, 1, order.long())
+            scores[:, :kw] = best
+            out["settled_first_pass"] = int(done.sum())
+            todo = torch.from_numpy(np.flatnonzero(~done)).to(dev)
+        if q and kk and (todo is None or int(todo.numel())):
+            if d_ids is None:
+                live_rows = torch.arange(m, dtype=torch.int64, device=dev)
+                live_ids = live_rows
+            else:
+                live_rows = torch.nonzero(d_ids >= 0).reshape(-1)
+                live_ids = d_ids[live_rows]
+                by_id = torch.argsort(live_ids)
+                live_rows, live_ids = live_rows[by_id].contiguous(), live_ids[by_id].contiguous()
+            sub = d_q if todo is None else d_q[todo].contiguous()
+            g_ids, g_scores = _gather(torch, corpus, sub, live_rows, live_ids, kk)
+            if todo is None:
+                ids, scores = g_ids, g_scores
+            else:
+                ids[todo], scores[todo] = g_ids, g_scores
+            out["gathered"] = int(sub.shape[0])
+    if stats is not None:
+        stats.clear()
+        stats.update(out)
+    if return_tensors:
+        return ids, scores
+    return ids.cpu().numpy(), scores.cpu().numpy()

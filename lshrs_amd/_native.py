@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 # one translation unit per kernel family (what they share: csrc/lshrs_common.h); pipeline.hip: the native driver of the host-engine route
-UNITS = ("sig_setup", "sig_f32", "sig16", "sig16r", "sig_replay", "sig_small", "sig_split", "storage", "rerank", "query", "idmap", "pipeline")
+UNITS = ("sig_setup", "sig_f32", "sig16", "sig16r", "sig_replay", "sig_small", "sig_split", "storage", "rerank", "query", "idmap", "scan", "pipeline")
 SOURCES = tuple(os.path.join(CSRC, u + ".hip") for u in UNITS)
 SOURCE = SOURCES[0]
 # (LSHRS_HIP_LIBRARY: load another build of the same ABI instead - A/B measurements of compiler flags, tools/ab_build.py)
@@ -32,6 +32,8 @@ SORT_MAX_COLS = 1024      # kSortMaxCols of csrc/lshrs_common.h: padded key colu
 
 BUILD_WRONG_KEYS = 0x1   # LSHRS_BUILD_WRONG_KEYS
 BUILD_TUNED = 0x2        # LSHRS_BUILD_TUNED
+
+SCAN_ELEMS = ("f32", "bf16", "f16", "i8", "f8e4m3")   # LSHRS_SCAN_F32 .. LSHRS_SCAN_F8E4M3, in that order
 
 E_BADARG = -10001
 E_TOOLARGE = -10002
@@ -208,6 +210,17 @@ def _declare(lib: ctypes.CDLL) -> None:
     # (src, src_slots, dst, dst_slots, report, stream)
     lib.lshrs_idmap_rehash.argtypes = [vp, i64, vp, i64, vp, vp]
     lib.lshrs_idmap_rehash.restype = c.c_int
+    # the exhaustive scan of a row block on the matrix cores (csrc/scan.hip)
+    lib.lshrs_scan_workspace_bytes.argtypes = [i32, i64, i32, i32]
+    lib.lshrs_scan_workspace_bytes.restype = i64
+    lib.lshrs_scan_max_window.argtypes = []
+    lib.lshrs_scan_max_window.restype = i32
+    lib.lshrs_scan_epsilon.argtypes = [i32, i32]
+    lib.lshrs_scan_epsilon.restype = f64
+    # (corpus, m, ldc, dim, row_ids, queries, q, window, out_rows, out_approx, out_count, workspace, err, stream)
+    for dt in SCAN_ELEMS:
+        scan = getattr(lib, "lshrs_scan_topk_" + dt)
+        scan.argtypes, scan.restype = [vp, i64, i64, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp], c.c_int
     lib.lshrs_pipe_create.argtypes = [i32, i32, i32, i32, i32]
     lib.lshrs_pipe_create.restype = vp
     lib.lshrs_pipe_destroy.argtypes = [vp]
@@ -268,6 +281,14 @@ EXPORTS = (
     "lshrs_idmap_lookup_i64",
     "lshrs_idmap_lookup_ragged_i64",
     "lshrs_idmap_rehash",
+    "lshrs_scan_workspace_bytes",
+    "lshrs_scan_max_window",
+    "lshrs_scan_epsilon",
+    "lshrs_scan_topk_f32",
+    "lshrs_scan_topk_bf16",
+    "lshrs_scan_topk_f16",
+    "lshrs_scan_topk_i8",
+    "lshrs_scan_topk_f8e4m3",
     "lshrs_pipe_create",
     "lshrs_pipe_destroy",
     "lshrs_pipe_hash_f32",

@@ -209,6 +209,7 @@ class LSHRS:
         if self._vectors is not None and self._vectors.dim != dim:
             raise ValueError(f"keep_vectors holds vectors of dimension {self._vectors.dim}; the index has {dim}")
         self.last_query_stats: Dict[str, Any] = {}
+        self.last_search_stats: Dict[str, Any] = {}     # what the last search_exact did (lshrs_amd.exact_top_k's stats)
         from ._query_device import DeviceBuckets
 
         self._dev_buckets = DeviceBuckets()  # device mirror of the store's bucket arrays (query_many)
@@ -602,6 +603,61 @@ class LSHRS:
             if scores is None:
                 return qh.split_rows(ids.tolist(), keep)
             return qh.split_rows(list(zip(ids.tolist(), scores.astype(np.float64).tolist())), keep)
+
+    def search_exact(self, vectors, top_k: int = 10, *, return_arrays: bool = False):
+        """The ``top_k`` indexed vectors nearest to every query by cosine, EXACTLY: every vector of the attached corpus
+        (:meth:`set_corpus`), else of the index's own store (``keep_vectors``), is scored - no buckets involved
+        (``lshrs_amd.exact_top_k``: one pass over the rows on the matrix cores, the survivors rescored by the rerank's kernel).
+        The ground truth for :meth:`recall`, and the answer where the buckets of a query hold fewer than ``top_k`` members.
+        ``vectors``: as in :meth:`query_many`.  Returns per query ``[(id, score), ...]``, scores descending and equal scores by
+        ascending id - or ``(ids (n, kk) int64, scores (n, kk) float32)`` with ``return_arrays``; ``kk = min(top_k, vectors
+        there)``.  Without a corpus or a store it raises what a rerank without a fetch function raises.  ``last_search_stats``
+        tells what the call did.  A corpus that :meth:`set_corpus` was given as a HOST array is uploaded by every call, as every
+        reranked query uploads it (and twice by :meth:`recall`, once for each of its halves): attach a device tensor."""
+        resident = _device_tensor(vectors)
+        arr = resident if resident is not None else np.asarray(vectors, dtype=np.float32)
+        if len(arr.shape) != 2 or int(arr.shape[1]) != self._dim:
+            raise ValueError(f"Vectors must have shape (n, {self._dim}); received {tuple(arr.shape)}")
+        if resident is not None:
+            arr = resident.float()
+        qh.check_cut(top_k, None)
+        if top_k is None:
+            raise ValueError("search_exact needs a top_k")
+        corpus = self._rerank_corpus()
+        if corpus is None:
+            self._require_vector_fetch_fn()
+            raise RuntimeError("search_exact needs the indexed vectors on the device: set_corpus(...) or keep_vectors=...")
+        if isinstance(corpus, DeviceVectors):
+            ids, scores = corpus.search(arr, top_k)
+            self.last_search_stats = dict(corpus.last_search_stats)
+        else:
+            from . import _query_device as qd
+            from ._exact import exact_top_k
+
+            stats: Dict[str, Any] = {}
+            table = qd.corpus_on(corpus, getattr(corpus, "device", None) if _device_tensor(corpus) is not None
+                                 else self._hasher._torch_device(), self._dim)
+            ids, scores = exact_top_k(arr, table, top_k, stats=stats)
+            self.last_search_stats = stats
+        if return_arrays:
+            return ids, scores
+        with _gc_paused():
+            return [list(zip(i, s)) for i, s in zip(ids.tolist(), scores.astype(np.float64).tolist())]
+
+    def recall(self, vectors, *, top_k: int = 10, top_p: Optional[float] = None) -> Dict[str, Any]:
+        """How much of the true top ``top_k`` the index returns for these queries: :meth:`query_many` ``(vectors, top_k=top_k,
+        top_p=top_p)`` against :meth:`search_exact` ``(vectors, top_k)``.  Returns ``{"recall": mean over the queries of |LSH
+        ids & exact ids| / len(exact ids), "per_query": that ratio per query (float32), "exact": the exact ids (n, kk),
+        "returned": mean length of the LSH answers}``.  What ``num_bands x rows_per_band`` buys on a corpus, measured."""
+        got_ids, _, bounds = self.query_many(vectors, top_k=top_k, top_p=top_p, return_arrays=True)
+        exact, _ = self.search_exact(vectors, top_k, return_arrays=True)
+        n = int(exact.shape[0])
+        per = np.zeros(n, dtype=np.float32)
+        for i in range(n):
+            if exact.shape[1]:
+                per[i] = np.intersect1d(got_ids[bounds[i]:bounds[i + 1]], exact[i]).shape[0] / exact.shape[1]
+        return {"recall": float(per.mean()) if n else 0.0, "per_query": per, "exact": exact,
+                "returned": float(np.diff(bounds).mean()) if n else 0.0}
 
     def _query_many_device(self, arr, top_k, top_p, corpus):
         """``query_many`` with everything between the upload of the queries and the download of the answers on the device."""

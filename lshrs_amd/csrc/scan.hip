@@ -1,0 +1,629 @@
+// scan.hip - part of liblshrs_hip.so, the gfx950 (MI355X / CDNA4) implementation of the lshrs hot path.
+// K6 exhaustive scan: every row of a device-resident (m, dim) block against a tile of 64 queries on the matrix cores
+// (v_mfma_f32_32x32x16_bf16), keeping per query the `window` rows of the largest APPROXIMATE cosine.  The caller rescores the
+// window exactly (lshrs_cosine_ragged_*) and settles the answer with lshrs_scan_epsilon (lshrs_amd/_exact.py).
+//
+// One workgroup = four waves = (a slice of the rows) x (64 queries).  A pass takes 256 rows, 64 per wave as two 32-row MFMA
+// tiles.  The rows are the A operand, read from global memory straight into the registers the instruction wants (a lane's
+// eight k-values of one row are contiguous: no LDS); the queries are the B operand, split once per launch into two bf16
+// terms (hi = the f32's upper 16 bits, mid = the upper 16 bits of q - hi) and laid out in fragment order by
+// scan_prep_kernel, staged through LDS in chunks of 64 k so that any dim fits.  Within a chunk the lanes' halves take k in
+// [32h, 32h + 32): MFMA step s multiplies k = 32h + 8s + j on both operands - a permutation of k, which a sum over k does not
+// see - so that a lane's 32 elements of a row are ONE contiguous run (64 bytes of bf16).
+// bf16, int8 and e4m3fn rows are exact in bf16 (one term); f16 and f32 rows enter as two terms (x_hi q_hi + x_hi q_mid +
+// x_mid q_hi).  ||x||^2 is summed in f32 from the elements already in registers.  One-term rows: chunk c + 1's loads are
+// issued before chunk c is multiplied.
+// Selection: per query a buffer of `cap` 64-bit items {orderable score, ~row} - cap = the power of two at or above 2 * window,
+// at least 64 - and a threshold item in LDS.  A finished output tile pushes what beats the threshold (an LDS ticket per
+// query); when a buffer is full the workgroup prunes it to its `window` largest by rank counting (items in registers, handed
+// round the wave by v_readlane) and raises the threshold.  Each slice leaves its sorted winners in the workspace;
+// scan_merge_kernel orders the slices' winners of a query in LDS.  No global atomics but the error bits.
+// ABI and reference citations: include/lshrs_hip.h.  Design notes, the epsilon derivation and the roof: DESIGN.md.
+#include "lshrs_common.h"
+
+#include <type_traits>
+
+using namespace lshrs;
+
+namespace {
+constexpr int kScanThreads = 256;
+constexpr int kScanWaves = 4;
+constexpr int kScanQTile = 64;        // queries per workgroup (two 32-column B blocks)
+constexpr int kScanKChunk = 64;       // k per staged B chunk (four MFMA steps of 16)
+constexpr int kScanPassRows = 256;    // rows per workgroup pass: 64 per wave, two 32-row tiles
+constexpr int kScanMaxWindow = 128;
+constexpr int kScanChunkBytes = kScanQTile * kScanKChunk * 2 * 2;   // both terms: 16 KiB
+constexpr int kScanMaxDim = 16384;
+constexpr int kScanMergeItems = 8192; // slices * window a merge workgroup sorts in LDS (64 KiB)
+
+struct Bf16 {};
+struct F16 {};
+struct I8 {};
+struct F8E4M3 {};
+
+// per element type: what a row holds, bf16 terms per element, 16-B vectors behind a lane's 32 elements of a chunk
+template <typename E> struct ScanElem;
+template <> struct ScanElem<float> { using T = float; static constexpr int kTerms = 2, kVecs = 8, kAlign = 4; };
+template <> struct ScanElem<Bf16> { using T = uint16_t; static constexpr int kTerms = 1, kVecs = 4, kAlign = 8; };
+template <> struct ScanElem<F16> { using T = uint16_t; static constexpr int kTerms = 2, kVecs = 4, kAlign = 8; };
+template <> struct ScanElem<I8> { using T = int8_t; static constexpr int kTerms = 1, kVecs = 2, kAlign = 16; };
+template <> struct ScanElem<F8E4M3> { using T = uint8_t; static constexpr int kTerms = 1, kVecs = 2, kAlign = 16; };
+
+template <typename E> struct ScanRaw { u32x4 v[ScanElem<E>::kVecs]; };   // 32 elements as they lie in memory
+
+__device__ __forceinline__ float scan_wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// ascending-orderable bits of a score; an item = {key, ~row}: larger = better score, then lower row.  0 = no item (every real
+// key is above 0: the key of -inf is 0x007fffff).
+__device__ __forceinline__ uint32_t scan_key(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float scan_unkey(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// ------------------------------------------------------------------------------------------
+// queries -> B fragments.  Workspace image: [qtile][chunk][term][step s][column block cb][lane] x 16 bytes; lane (c = l & 31,
+// h = l >> 5) holds query qtile * 64 + cb * 32 + c at k = chunk * 64 + 32 h + 8 s + j, j = 0 .. 7.  Zero beyond q and dim.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kScanThreads) void scan_prep_kernel(const float* __restrict__ queries, int q, int dim, int nchunks,
+                                                                 u32x4* __restrict__ image) {
+  const int chunk = blockIdx.x, qtile = blockIdx.y;
+  u32x4* out = image + ((int64_t)qtile * nchunks + chunk) * (kScanChunkBytes / 16);
+  for (int f = threadIdx.x; f < 512; f += kScanThreads) {
+    const int lane = f & 63, cb = (f >> 6) & 1, s = f >> 7;
+    const int qi = qtile * kScanQTile + cb * 32 + (lane & 31);
+    const int kbase = chunk * kScanKChunk + 32 * (lane >> 5) + 8 * s;
+    uint32_t hb[8], mb[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int k = kbase + j;
+      const float v = (qi < q && k < dim) ? queries[(int64_t)qi * dim + k] : 0.f;
+      const uint32_t b = __float_as_uint(v) & 0xffff0000u;
+      hb[j] = b >> 16;
+      mb[j] = __float_as_uint(v - __uint_as_float(b)) >> 16;
+    }
+    u32x4 hi, mid;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      hi[d] = hb[2 * d] | (hb[2 * d + 1] << 16);
+      mid[d] = mb[2 * d] | (mb[2 * d + 1] << 16);
+    }
+    out[((0 * 4 + s) * 2 + cb) * 64 + lane] = hi;
+    out[((1 * 4 + s) * 2 + cb) * 64 + lane] = mid;
+  }
+}
+
+// ||q|| in f32, one wave per query (1 for the padding queries of the last tile); err |= 4 for a query of zero norm
+__global__ __launch_bounds__(kScanThreads) void scan_qnorm_kernel(const float* __restrict__ queries, int q, int qpad, int dim,
+                                                                  float* __restrict__ qnorm, int32_t* __restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int qi = blockIdx.x * kScanWaves + (threadIdx.x >> 6);
+  if (qi >= qpad) return;
+  float ss = 0.f;
+  if (qi < q)
+    for (int k = lane; k < dim; k += 64) {
+      const float v = queries[(int64_t)qi * dim + k];
+      ss = __builtin_fmaf(v, v, ss);
+    }
+  ss = scan_wave_sum(ss);
+  if (lane == 0) {
+    const float n = qi < q ? sqrtf(ss) : 1.f;
+    qnorm[qi] = n;
+    if (n == 0.f && err != nullptr) atomicOr(err, 4);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// a lane's 32 elements of one row of one chunk, as they lie in memory
+// ------------------------------------------------------------------------------------------
+template <typename E>
+__device__ __forceinline__ ScanRaw<E> scan_load_vec(const typename ScanElem<E>::T* p) {
+  ScanRaw<E> r;
+  const u32x4* v = reinterpret_cast<const u32x4*>(p);
+#pragma unroll
+  for (int i = 0; i < ScanElem<E>::kVecs; ++i) r.v[i] = v[i];
+  return r;
+}
+
+// the same image built element by element: any address and stride, nothing read at k >= dim (zero bits are 0.0 in all five types)
+template <typename E>
+__device__ __forceinline__ ScanRaw<E> scan_load_elems(const typename ScanElem<E>::T* row, int k0, int dim) {
+  using T = typename ScanElem<E>::T;
+  constexpr int kPer = 4 / (int)sizeof(T);            // elements per dword
+  ScanRaw<E> r;
+#pragma unroll
+  for (int i = 0; i < ScanElem<E>::kVecs; ++i)
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      uint32_t w = 0;
+#pragma unroll
+      for (int e = 0; e < kPer; ++e) {
+        const int k = k0 + (i * 4 + d) * kPer + e;
+        if (k < dim) {
+          uint32_t bits;
+          if constexpr (sizeof(T) == 4) bits = __float_as_uint(row[k]);
+          else bits = (uint32_t)row[k] & ((1u << (8 * sizeof(T) % 32)) - 1u);
+          w |= bits << (8 * (int)sizeof(T) * e % 32);
+        }
+      }
+      r.v[i][d] = w;
+    }
+  return r;
+}
+
+// the eight elements of MFMA step s as f32 (exact)
+__device__ __forceinline__ void scan_elems8(float, const ScanRaw<float>& r, int s, float (&x)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = __uint_as_float(r.v[2 * s + (j >> 2)][j & 3]);
+}
+__device__ __forceinline__ void scan_elems8(F16, const ScanRaw<F16>& r, int s, float (&x)[8]) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const uint32_t w = r.v[s][d];
+    x[2 * d] = (float)__builtin_bit_cast(_Float16, (uint16_t)w);
+    x[2 * d + 1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
+  }
+}
+__device__ __forceinline__ void scan_elems8(I8, const ScanRaw<I8>& r, int s, float (&x)[8]) {
+#pragma unroll
+  for (int d = 0; d < 2; ++d) {
+    const uint32_t w = r.v[s >> 1][(s & 1) * 2 + d];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[4 * d + j] = (float)(int8_t)(w >> (8 * j));
+  }
+}
+__device__ __forceinline__ void scan_elems8(F8E4M3, const ScanRaw<F8E4M3>& r, int s, float (&x)[8]) {
+#pragma unroll
+  for (int d = 0; d < 2; ++d) {
+    const uint32_t w = r.v[s >> 1][(s & 1) * 2 + d];
+    x[4 * d + 0] = __builtin_amdgcn_cvt_f32_fp8((int)w, 0);
+    x[4 * d + 1] = __builtin_amdgcn_cvt_f32_fp8((int)w, 1);
+    x[4 * d + 2] = __builtin_amdgcn_cvt_f32_fp8((int)w, 2);
+    x[4 * d + 3] = __builtin_amdgcn_cvt_f32_fp8((int)w, 3);
+  }
+}
+
+// raw elements -> the A fragments of the four steps (hi; mid for the two-term types) and += ||x||^2
+template <typename E>
+__device__ __forceinline__ void scan_fragments(const ScanRaw<E>& r, u32x4 (&hi)[4], u32x4 (&mid)[4], float& nn) {
+  if constexpr (std::is_same_v<E, Bf16>) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      hi[s] = r.v[s];
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const float a = __uint_as_float(r.v[s][d] << 16), b = __uint_as_float(r.v[s][d] & 0xffff0000u);
+        nn = __builtin_fmaf(a, a, nn);
+        nn = __builtin_fmaf(b, b, nn);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      float x[8];
+      scan_elems8(E{}, r, s, x);
+      uint32_t hb[8], mb[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        nn = __builtin_fmaf(x[j], x[j], nn);
+        const uint32_t b = __float_as_uint(x[j]) & 0xffff0000u;
+        hb[j] = b;
+        if constexpr (ScanElem<E>::kTerms == 2) mb[j] = __float_as_uint(x[j] - __uint_as_float(b)) & 0xffff0000u;
+      }
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        hi[s][d] = (hb[2 * d] >> 16) | hb[2 * d + 1];
+        if constexpr (ScanElem<E>::kTerms == 2) mid[s][d] = (mb[2 * d] >> 16) | mb[2 * d + 1];
+      }
+    }
+  }
+}
+
+// One query's buffer to its `window` largest items, sorted descending, by one wave.  The items go to registers (NI = cap / 64 per
+// lane); every lane ranks its own against all of them, which the wave hands round lane by lane (v_readlane: no LDS round trip
+// per item); the kept ones go to their ranks.  Items are distinct (their rows are), so the ranks are a permutation.
+template <int NI>
+__device__ __forceinline__ void scan_prune_n(uint64_t* buf, int n, int window, uint64_t* thr, int* cnt, int lane) {
+  uint32_t lo[NI], hi[NI];
+  uint64_t mine[NI];
+  int rank[NI];
+#pragma unroll
+  for (int j = 0; j < NI; ++j) {
+    const int idx = lane + 64 * j;
+    mine[j] = idx < n ? buf[idx] : 0ull;
+    lo[j] = (uint32_t)mine[j];
+    hi[j] = (uint32_t)(mine[j] >> 32);
+    rank[j] = 0;
+  }
+#pragma unroll
+  for (int c = 0; c < NI; ++c) {
+    if (64 * c >= n) break;                            // (uniform: n is the same in every lane)
+#pragma unroll 8
+    for (int i = 0; i < 64; ++i) {
+      const uint64_t v = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hi[c], i) << 32) |
+                         (uint32_t)__builtin_amdgcn_readlane((int)lo[c], i);
+#pragma unroll
+      for (int j = 0; j < NI; ++j) rank[j] += v > mine[j] ? 1 : 0;      // (an empty place is 0: it outranks nothing)
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NI; ++j)
+    if (mine[j] != 0ull && rank[j] < window) {
+      buf[rank[j]] = mine[j];
+      if (rank[j] == window - 1) *thr = mine[j];
+    }
+  if (lane == 0) *cnt = min(n, window);
+}
+
+// `all`: sort even when nothing has to go (the slice's last call).  cap is 64, 128 or 256 (scan_plan).
+__device__ __forceinline__ void scan_prune(uint64_t* buf, int cap, int window, uint64_t* thr, int* cnt, int lane, bool all) {
+  const int n = min(*cnt, cap);
+  if (n <= window && !all) return;
+  if (cap <= 64) scan_prune_n<1>(buf, n, window, thr, cnt, lane);
+  else if (cap <= 128) scan_prune_n<2>(buf, n, window, thr, cnt, lane);
+  else scan_prune_n<4>(buf, n, window, thr, cnt, lane);
+}
+
+// ------------------------------------------------------------------------------------------
+// the scan.  grid (slices, query tiles); dynamic LDS: B chunk | items [64][cap] | threshold [64] | count [64]
+// ------------------------------------------------------------------------------------------
+template <typename E, bool ALIGNED>
+__global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename ScanElem<E>::T* __restrict__ corpus, int64_t m,
+                                                            int64_t ldc, int dim, const int64_t* __restrict__ row_ids,
+                                                            const u32x4* __restrict__ image, const float* __restrict__ qnorm,
+                                                            int q, int window, int cap, int64_t rows_per_slice,
+                                                            uint64_t* __restrict__ parts, int32_t* __restrict__ err) {
+  using T = typename ScanElem<E>::T;
+  constexpr bool kTwo = ScanElem<E>::kTerms == 2;
+  extern __shared__ __attribute__((aligned(16))) unsigned char scan_lds[];
+  u32x4* bl = reinterpret_cast<u32x4*>(scan_lds);
+  uint64_t* items = reinterpret_cast<uint64_t*>(scan_lds + kScanChunkBytes);
+  uint64_t* thr = items + (size_t)kScanQTile * cap;
+  int* cnt = reinterpret_cast<int*>(thr + kScanQTile);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int slice = blockIdx.x, slices = gridDim.x, qtile = blockIdx.y;
+  const int nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
+  const int64_t row_begin = (int64_t)slice * rows_per_slice;
+  const int64_t row_end = min(m, row_begin + rows_per_slice);
+  const u32x4* bimg = image + (int64_t)qtile * nchunks * (kScanChunkBytes / 16);
+
+  if (tid < kScanQTile) {
+    thr[tid] = 0ull;
+    cnt[tid] = 0;
+  }
+  float qn[2];
+  bool qok[2];
+#pragma unroll
+  for (int cb = 0; cb < 2; ++cb) {
+    const int qi = qtile * kScanQTile + cb * 32 + r;
+    qok[cb] = qi < q;
+    qn[cb] = qnorm[qi];                   // (padded to whole tiles)
+  }
+  __syncthreads();
+
+  for (int64_t base = row_begin; base < row_end; base += kScanPassRows) {
+    const T* rowp[2];
+    bool live[2];
+    int64_t row0[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      row0[t] = base + wave * 64 + t * 32;
+      const int64_t row = row0[t] + r;
+      const bool valid = row < row_end;
+      live[t] = valid && (row_ids == nullptr || row_ids[row] >= 0);
+      rowp[t] = corpus + (valid ? row : row_begin) * ldc;      // (a row past the end reads the slice's first row, unused)
+    }
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][cb][i] = 0.f;
+    float nn[2] = {0.f, 0.f};
+
+    // chunk c + 1's rows and B fragments are asked for before chunk c is multiplied, so that the loads fly under the MFMAs
+    auto load_chunk = [&](int c, ScanRaw<E> (&raw)[2], u32x4 (&bst)[4]) {
+      const int k0 = c * kScanKChunk + 32 * h;
+      if (ALIGNED && (c + 1) * kScanKChunk <= dim) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) raw[t] = scan_load_vec<E>(rowp[t] + k0);
+      } else {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) raw[t] = scan_load_elems<E>(rowp[t], k0, dim);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) bst[i] = bimg[(int64_t)c * (kScanChunkBytes / 16) + i * kScanThreads + tid];
+    };
+    // (one-term rows only: a two-term row's fragments leave no registers for a second chunk)
+    constexpr bool kAhead = !kTwo;
+    ScanRaw<E> nraw[2];
+    u32x4 nbst[4];
+    if constexpr (kAhead) load_chunk(0, nraw, nbst);
+    for (int c = 0; c < nchunks; ++c) {
+      if constexpr (!kAhead) load_chunk(c, nraw, nbst);
+      ScanRaw<E> raw[2] = {nraw[0], nraw[1]};
+      __syncthreads();                    // the last chunk's fragments have been read
+#pragma unroll
+      for (int i = 0; i < 4; ++i) bl[i * kScanThreads + tid] = nbst[i];
+      __syncthreads();
+      if constexpr (kAhead)
+        if (c + 1 < nchunks) load_chunk(c + 1, nraw, nbst);
+
+      u32x4 ahi[2][4], amid[2][4];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) scan_fragments<E>(raw[t], ahi[t], amid[t], nn[t]);
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+          const bf16x8 bh = __builtin_bit_cast(bf16x8, bl[((0 * 4 + s) * 2 + cb) * 64 + lane]);
+          const bf16x8 bm = __builtin_bit_cast(bf16x8, bl[((1 * 4 + s) * 2 + cb) * 64 + lane]);
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            const bf16x8 ah = __builtin_bit_cast(bf16x8, ahi[t][s]);
+            acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t][cb], 0, 0, 0);
+            acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[t][cb], 0, 0, 0);
+            if constexpr (kTwo)
+              acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, amid[t][s]), bh, acc[t][cb], 0, 0, 0);
+          }
+        }
+    }
+
+    // the finished 256 x 64 tile: acc[t][cb][i] is row (i & 3) + 8 (i >> 2) + 4 h of tile t, query cb * 32 + r
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      nn[t] += __shfl_xor(nn[t], 32);
+      const float xn = sqrtf(nn[t]);
+      if (live[t] && xn == 0.f && h == 0 && err != nullptr) atomicOr(err, 1);
+      const uint32_t livemask = (uint32_t)__ballot(live[t]);
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        const int qc = cb * 32 + r;
+        uint64_t* buf = items + (size_t)qc * cap;
+        // (the scores replace the dot products in the accumulator; an item is rebuilt from its score where it is needed)
+        const uint32_t rowlo = 0xffffffffu - (uint32_t)(row0[t] + 4 * h);
+        uint32_t pend = 0;
+        uint64_t bar = thr[qc];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int rr = (i & 3) + 8 * (i >> 2) + 4 * h;
+          const float rn = __shfl(xn, rr);
+          const float sc = acc[t][cb][i] / (rn * qn[cb]);
+          acc[t][cb][i] = sc;
+          const uint64_t it = ((uint64_t)scan_key(sc) << 32) | (rowlo - (uint32_t)((i & 3) + 8 * (i >> 2)));
+          if (qok[cb] && ((livemask >> rr) & 1u) && sc == sc && it > bar) pend |= 1u << i;
+        }
+        for (;;) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (pend & (1u << i)) {
+              const int pos = atomicAdd(&cnt[qc], 1);
+              if (pos < cap) {
+                buf[pos] = ((uint64_t)scan_key(acc[t][cb][i]) << 32) | (rowlo - (uint32_t)((i & 3) + 8 * (i >> 2)));
+                pend &= ~(1u << i);
+              }
+            }
+          if (!__syncthreads_or(pend != 0)) break;
+          // a buffer overflowed: every wave prunes its share of the queries, then those left out try again
+          for (int qq = wave; qq < kScanQTile; qq += kScanWaves)
+            scan_prune(items + (size_t)qq * cap, cap, window, thr + qq, cnt + qq, lane, false);
+          __syncthreads();
+          bar = thr[qc];
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const uint64_t it = ((uint64_t)scan_key(acc[t][cb][i]) << 32) | (rowlo - (uint32_t)((i & 3) + 8 * (i >> 2)));
+            if (!(it > bar)) pend &= ~(1u << i);
+          }
+        }
+      }
+    }
+  }
+
+  // the slice's winners of every query, sorted, zero items behind them
+  __syncthreads();
+  for (int qq = wave; qq < kScanQTile; qq += kScanWaves) {
+    const int qi = qtile * kScanQTile + qq;
+    if (qi >= q) continue;
+    uint64_t* buf = items + (size_t)qq * cap;
+    scan_prune(buf, cap, window, thr + qq, cnt + qq, lane, true);
+    const int kept = cnt[qq];
+    uint64_t* out = parts + ((int64_t)qi * slices + slice) * window;
+    for (int j = lane; j < window; j += 64) out[j] = j < kept ? buf[j] : 0ull;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// one workgroup per query: the slices' winners into LDS, bitonic network descending, the first `window` out
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kScanThreads) void scan_merge_kernel(const uint64_t* __restrict__ parts, int n, int npad, int window,
+                                                                  int64_t* __restrict__ out_rows, float* __restrict__ out_approx,
+                                                                  int32_t* __restrict__ out_count) {
+  extern __shared__ __attribute__((aligned(16))) uint64_t merge_items[];
+  __shared__ int total;
+  const int qi = blockIdx.x;
+  const uint64_t* src = parts + (int64_t)qi * n;
+  if (threadIdx.x == 0) total = 0;
+  for (int t = threadIdx.x; t < npad; t += kScanThreads) merge_items[t] = t < n ? src[t] : 0ull;
+  __syncthreads();
+  for (int size = 2; size <= npad; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < (npad >> 1); t += kScanThreads) {
+        const int lo = 2 * t - (t & (stride - 1));
+        const int hi = lo + stride;
+        const bool up = ((lo & size) == 0);
+        const uint64_t a = merge_items[lo], b = merge_items[hi];
+        if ((a < b) == up) {
+          merge_items[lo] = b;
+          merge_items[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+  int have = 0;
+  for (int t = threadIdx.x; t < window; t += kScanThreads) {     // (window <= n <= npad)
+    const uint64_t v = merge_items[t];
+    have += v != 0ull ? 1 : 0;
+    out_rows[(int64_t)qi * window + t] = v != 0ull ? (int64_t)(0xffffffffu - (uint32_t)v) : -1;
+    out_approx[(int64_t)qi * window + t] = v != 0ull ? scan_unkey((uint32_t)(v >> 32)) : -__builtin_inff();
+  }
+  if (have) atomicAdd(&total, have);
+  __syncthreads();
+  if (threadIdx.x == 0) out_count[qi] = total;
+}
+
+// ------------------------------------------------------------------------------------------
+// host side: geometry of a launch, shared by the workspace size and the entries
+// ------------------------------------------------------------------------------------------
+struct ScanPlan {
+  int qtiles, nchunks, slices, cap;
+  int64_t rows_per_slice;
+  int64_t image_bytes, qnorm_bytes, parts_bytes;
+};
+
+inline int scan_plan(int32_t q, int64_t m, int32_t dim, int32_t window, ScanPlan& p) {
+  if (q < 0 || m <= 0 || dim <= 0 || window <= 0 || window > kScanMaxWindow) return LSHRS_E_BADARG;
+  if (dim > kScanMaxDim || m > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
+  p.qtiles = (q + kScanQTile - 1) / kScanQTile;
+  if (p.qtiles > 65535) return LSHRS_E_TOOLARGE;
+  p.nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
+  p.cap = 64;
+  while (p.cap < 2 * window) p.cap <<= 1;
+  // slices: one round of the workgroups that are resident at a time - 256 CUs, two per CU while their LDS fits twice into the
+  // CU's 160 KiB, else one - over all query tiles: a second, part-filled round costs a whole slice's time.  At least 1024
+  // rows each, and no more than one merge workgroup sorts in LDS.
+  const int64_t lds = (int64_t)kScanChunkBytes + (int64_t)kScanQTile * p.cap * 8 + kScanQTile * 12;
+  const int64_t resident = 256 * (2 * lds <= 160 * 1024 ? 2 : 1);
+  const int64_t qt = p.qtiles > 0 ? p.qtiles : 1;
+  int64_t want = resident / qt;
+  const int64_t by_rows = (m + 1023) / 1024;
+  if (want > by_rows) want = by_rows;
+  if (want > kScanMergeItems / window) want = kScanMergeItems / window;
+  if (want < 1) want = 1;
+  const int64_t passes = (m + kScanPassRows - 1) / kScanPassRows;
+  const int64_t rps = (passes + want - 1) / want * kScanPassRows;
+  p.rows_per_slice = rps;
+  p.slices = (int)((m + rps - 1) / rps);
+  p.image_bytes = (int64_t)p.qtiles * p.nchunks * kScanChunkBytes;
+  p.qnorm_bytes = (int64_t)p.qtiles * kScanQTile * (int64_t)sizeof(float);
+  p.parts_bytes = (int64_t)q * p.slices * window * (int64_t)sizeof(uint64_t);
+  return 0;
+}
+
+template <typename E, bool ALIGNED>
+int scan_launch(const ScanPlan& p, const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim,
+                const int64_t* row_ids, const u32x4* image, const float* qnorm, int32_t q, int32_t window, uint64_t* parts,
+                int32_t* err, hipStream_t s) {
+  const size_t shmem = (size_t)kScanChunkBytes + (size_t)kScanQTile * p.cap * 8 + kScanQTile * 8 + kScanQTile * 4;
+  if (shmem > 48 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(scan_kernel<E, ALIGNED>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e != hipSuccess) return -(int)e;
+  }
+  hipLaunchKernelGGL((scan_kernel<E, ALIGNED>), dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(kScanThreads), shmem, s, corpus,
+                     m, ldc, dim, row_ids, image, qnorm, q, window, p.cap, p.rows_per_slice, parts, err);
+  return -(int)hipGetLastError();
+}
+
+template <typename E>
+int scan_topk(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids,
+              const float* queries, int32_t q, int32_t window, int64_t* out_rows, float* out_approx, int32_t* out_count,
+              void* workspace, int32_t* err, void* stream) {
+  if (q == 0) return 0;
+  ScanPlan p;
+  const int bad = scan_plan(q, m, dim, window, p);
+  if (bad) return bad;
+  if (corpus == nullptr || queries == nullptr || out_rows == nullptr || out_approx == nullptr || out_count == nullptr ||
+      workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 15) || ldc < dim)
+    return LSHRS_E_BADARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  u32x4* image = reinterpret_cast<u32x4*>(ws);
+  float* qnorm = reinterpret_cast<float*>(ws + p.image_bytes);
+  uint64_t* parts = reinterpret_cast<uint64_t*>(ws + p.image_bytes + p.qnorm_bytes);
+  const int qpad = p.qtiles * kScanQTile;
+  hipLaunchKernelGGL(scan_prep_kernel, dim3((unsigned)p.nchunks, (unsigned)p.qtiles), dim3(kScanThreads), 0, s, queries, q, dim,
+                     p.nchunks, image);
+  hipLaunchKernelGGL(scan_qnorm_kernel, dim3((unsigned)(qpad / kScanWaves)), dim3(kScanThreads), 0, s, queries, q, qpad, dim,
+                     qnorm, err);
+  constexpr int kAlign = ScanElem<E>::kAlign;
+  const bool aligned = (ldc % kAlign == 0) && ((reinterpret_cast<uintptr_t>(corpus) & 15) == 0);
+  const int rc = aligned ? scan_launch<E, true>(p, corpus, m, ldc, dim, row_ids, image, qnorm, q, window, parts, err, s)
+                         : scan_launch<E, false>(p, corpus, m, ldc, dim, row_ids, image, qnorm, q, window, parts, err, s);
+  if (rc) return rc;
+  const int n = p.slices * window;
+  int npad = 2;
+  while (npad < n) npad <<= 1;
+  const size_t merge_lds = (size_t)npad * sizeof(uint64_t);
+  if (merge_lds > 48 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(scan_merge_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)merge_lds);
+    if (e != hipSuccess) return -(int)e;
+  }
+  hipLaunchKernelGGL(scan_merge_kernel, dim3((unsigned)q), dim3(kScanThreads), merge_lds, s, parts, n, npad, window, out_rows,
+                     out_approx, out_count);
+  return -(int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" {
+
+int64_t lshrs_scan_workspace_bytes(int32_t q, int64_t m, int32_t dim, int32_t window) {
+  ScanPlan p;
+  const int bad = scan_plan(q, m, dim, window, p);
+  if (bad) return bad;
+  return p.image_bytes + p.qnorm_bytes + p.parts_bytes + 16;
+}
+
+int32_t lshrs_scan_max_window(void) { return kScanMaxWindow; }
+
+// The bound DESIGN.md derives: split + f32 accumulation, carried through the norm arithmetic.
+double lshrs_scan_epsilon(int32_t elem, int32_t dim) {
+  if (elem < LSHRS_SCAN_F32 || elem > LSHRS_SCAN_F8E4M3 || dim <= 0 || dim > kScanMaxDim) return -1.0;
+  const bool two = elem == LSHRS_SCAN_F32 || elem == LSHRS_SCAN_F16;
+  const double split = (two ? 3.0 : 1.0) * 0x1p-14;
+  const double products = (two ? 3.0 : 2.0) * kScanKChunk * ((dim + kScanKChunk - 1) / kScanKChunk);
+  const double acc = (1.0 + 0x1p-7) * (1.0 + 0x1p-7) * products * 0x1p-23 / (1.0 - products * 0x1p-23);
+  const double eta = (dim + 12.0) * 0x1p-24;
+  return ((split + acc) * (1.0 + eta) + eta) * 1.0625;
+}
+
+int lshrs_scan_topk_f32(const float* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, const float* queries,
+                        int32_t q, int32_t window, int64_t* out_rows, float* out_approx, int32_t* out_count, void* workspace,
+                        int32_t* err, void* stream) {
+  return scan_topk<float>(corpus, m, ldc, dim, row_ids, queries, q, window, out_rows, out_approx, out_count, workspace, err, stream);
+}
+
+int lshrs_scan_topk_bf16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, const float* queries,
+                         int32_t q, int32_t window, int64_t* out_rows, float* out_approx, int32_t* out_count, void* workspace,
+                         int32_t* err, void* stream) {
+  return scan_topk<Bf16>(corpus, m, ldc, dim, row_ids, queries, q, window, out_rows, out_approx, out_count, workspace, err, stream);
+}
+
+int lshrs_scan_topk_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, const float* queries,
+                        int32_t q, int32_t window, int64_t* out_rows, float* out_approx, int32_t* out_count, void* workspace,
+                        int32_t* err, void* stream) {
+  return scan_topk<F16>(corpus, m, ldc, dim, row_ids, queries, q, window, out_rows, out_approx, out_count, workspace, err, stream);
+}
+
+int lshrs_scan_topk_i8(const int8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, const float* queries,
+                       int32_t q, int32_t window, int64_t* out_rows, float* out_approx, int32_t* out_count, void* workspace,
+                       int32_t* err, void* stream) {
+  return scan_topk<I8>(corpus, m, ldc, dim, row_ids, queries, q, window, out_rows, out_approx, out_count, workspace, err, stream);
+}
+
+int lshrs_scan_topk_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids,
+                           const float* queries, int32_t q, int32_t window, int64_t* out_rows, float* out_approx,
+                           int32_t* out_count, void* workspace, int32_t* err, void* stream) {
+  return scan_topk<F8E4M3>(corpus, m, ldc, dim, row_ids, queries, q, window, out_rows, out_approx, out_count, workspace, err, stream);
+}
+
+}  // extern "C"

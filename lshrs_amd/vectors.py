@@ -86,6 +86,8 @@ class DeviceVectors:
         self._table = None          # (slots, 2) int64: {id, row} per slot, -1 = empty
         self._occupied = 0          # slots that hold an id (live or erased)
         self._live = 0              # ids that have a row
+        self._row_ids = None        # row -> id of the rows in use (-1: no id points at the row), built by search(); None = stale
+        self.last_search_stats: Dict[str, Any] = {}
 
     # ------------------------------------------------------------------ plumbing
     def _torch_dtype(self, torch):
@@ -133,7 +135,7 @@ class DeviceVectors:
         block = torch.empty((new_cap, self.dim), dtype=self._torch_dtype(torch), device=self._dev)
         if self._used:
             self._bytes_view(torch, block)[:self._used].copy_(self._bytes_view(torch, self._block)[:self._used])
-        self._block = block
+        self._block, self._row_ids = block, None
 
     def _ensure_slots(self, torch, incoming: int) -> None:
         """Room for ``incoming`` more ids: occupied slots - live and erased - stay at or below half of ``slots``."""
@@ -225,6 +227,7 @@ class DeviceVectors:
             self._occupied += fresh
             self._live += live
             self._used += n
+            self._row_ids = None
 
     def remove(self, ids) -> int:
         """Take ``ids`` out of the store (their rows stay until ``compact()``); returns how many were there."""
@@ -241,12 +244,13 @@ class DeviceVectors:
                           "lshrs_idmap_erase_i64")
             gone = int(count.item())
             self._live -= gone
+            self._row_ids = None
             return gone
 
     def clear(self) -> None:
         """Forget every id and row (the device memory goes back to the allocator)."""
         with self._lock:
-            self._block = self._table = None
+            self._block = self._table = self._row_ids = None
             self._used = self._occupied = self._live = 0
 
     def compact(self) -> None:
@@ -262,7 +266,7 @@ class DeviceVectors:
             block = torch.empty((cap, self.dim), dtype=self._torch_dtype(torch), device=self._dev)
             if live:
                 self._bytes_view(torch, block)[:live].copy_(torch.index_select(self._bytes_view(torch, self._block), 0, rows))
-            self._block, self._used, self._table = block, 0, None
+            self._block, self._used, self._table, self._row_ids = block, 0, None, None
             self._occupied = self._live = 0
             self._ensure_slots(torch, live)
             if live:
@@ -334,6 +338,38 @@ class DeviceVectors:
                     self._ensure_rows(torch, 1)
                     self._ensure_slots(torch, 0)
             return self._block[:max(self._used, 1)], self._table, int(self._table.shape[0])
+
+    def _search_snapshot(self):
+        """``(rows, row_ids)`` under the lock: the view :meth:`snapshot` hands out and, for each of its rows, the id that
+        points at it (int64, -1 for a superseded or erased row).  Built from the table's live pairs at the first search after
+        a write and kept until the next ``add`` / ``remove`` / ``compact`` / ``clear`` or swap of the block."""
+        torch = _native.require_gpu()
+        with self._lock:
+            rows, _, _ = self.snapshot()
+            if self._row_ids is None or int(self._row_ids.shape[0]) != int(rows.shape[0]):
+                with torch.cuda.device(self._dev):
+                    row_ids = torch.full((int(rows.shape[0]),), -1, dtype=torch.int64, device=self._dev)
+                    if self._live:
+                        ids, at = self._live_pairs(torch)
+                        row_ids[at] = ids
+                    self._row_ids = row_ids
+            return rows, self._row_ids
+
+    def search(self, queries, k: int = 10, *, method: str = "auto", return_tensors: bool = False):
+        """The ``k`` stored vectors nearest to every query by cosine, exactly, under the caller's ids: ``(ids (q, kk) int64,
+        scores (q, kk) float32)``, ``kk = min(k, len(self))`` - :func:`lshrs_amd.exact_top_k` over the row block where it is,
+        superseded and erased rows left out.  What the call did (queries settled by the first pass, queries gathered, window,
+        epsilon) is left in ``last_search_stats``."""
+        from ._exact import exact_top_k
+
+        shape = tuple(int(v) for v in getattr(queries, "shape", ())) or tuple(np.asarray(queries).shape)
+        if len(shape) != 2 or shape[1] != self.dim:
+            raise ValueError(f"Vectors must have shape (n, {self.dim}); received {shape}")
+        rows, row_ids = self._search_snapshot()
+        stats: Dict[str, Any] = {}
+        got = exact_top_k(queries, rows, k, row_ids=row_ids, method=method, return_tensors=return_tensors, stats=stats)
+        self.last_search_stats = stats
+        return got
 
     @property
     def rows(self):
