@@ -666,6 +666,34 @@ int lshrs_scan_topk_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_
                            const float* queries, int32_t q, int32_t window, int64_t* out_rows, float* out_approx,
                            int32_t* out_count, void* workspace, int32_t* err, void* stream);
 
+/* ---- range scan (csrc/scan.hip; lshrs_amd.exact_above): every (query, live row) whose APPROXIMATE cosine - the first pass
+ * of lshrs_scan_topk_*, same arithmetic, same epsilon - reaches the query's bar.  bars float[q]: a pair goes out when
+ * approx >= bars[qi] (a NaN score never does).  The pairs land, in no particular order, in three flat arrays of `capacity`
+ * slots: out_query int32 (the query), out_row int64 (the row), out_approx float (its approximate score); a pair whose slot
+ * would lie at or beyond `capacity` is counted and not written.  total: a device uint64_t, zeroed by the entry on the stream
+ * before the launch; afterwards the number of pairs that reached their bars, whether they fitted or not - a caller that finds
+ * total > capacity allocates `total` slots and calls once more.  capacity == 0 counts only (the three arrays may be null).
+ * row_ids, err, dim and m: as for lshrs_scan_topk_*.  capacity < 0, a null or misaligned argument: LSHRS_E_BADARG; q == 0
+ * returns 0 and touches nothing.  workspace: lshrs_scan_above_workspace_bytes(q, m, dim) bytes at a 16-byte aligned address.
+ * The caller that wants the rows whose RERANK score reaches t passes bars = t - (lshrs_scan_epsilon + the rerank's own rounding),
+ * rounded down, rescores what comes out and drops what is below t: nothing is missed.  (Additive to ABI 7.) */
+int64_t lshrs_scan_above_workspace_bytes(int32_t q, int64_t m, int32_t dim);
+int lshrs_scan_above_f32(const float* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids,
+                         const float* queries, int32_t q, const float* bars, int64_t capacity, int32_t* out_query,
+                         int64_t* out_row, float* out_approx, uint64_t* total, void* workspace, int32_t* err, void* stream);
+int lshrs_scan_above_bf16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids,
+                         const float* queries, int32_t q, const float* bars, int64_t capacity, int32_t* out_query,
+                         int64_t* out_row, float* out_approx, uint64_t* total, void* workspace, int32_t* err, void* stream);
+int lshrs_scan_above_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids,
+                         const float* queries, int32_t q, const float* bars, int64_t capacity, int32_t* out_query,
+                         int64_t* out_row, float* out_approx, uint64_t* total, void* workspace, int32_t* err, void* stream);
+int lshrs_scan_above_i8(const int8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids,
+                         const float* queries, int32_t q, const float* bars, int64_t capacity, int32_t* out_query,
+                         int64_t* out_row, float* out_approx, uint64_t* total, void* workspace, int32_t* err, void* stream);
+int lshrs_scan_above_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids,
+                         const float* queries, int32_t q, const float* bars, int64_t capacity, int32_t* out_query,
+                         int64_t* out_row, float* out_approx, uint64_t* total, void* workspace, int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

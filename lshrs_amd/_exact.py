@@ -15,6 +15,10 @@ The ground truth an approximate index is measured against (``LSHRS.recall``) and
 "gather"  the rerank's kernels over the list of all live rows: ``lshrs_cosine_batch_*`` then ``lshrs_topk_desc_f32``, in chunks of
           queries whose score matrix stays under 128 MiB (under 1 GiB with everything else a chunk allocates).  Every row is read once per query.
 
+``exact_above`` is the range search on the same first pass (``lshrs_scan_above_*``): every live row whose rerank score reaches a
+threshold.  No window, no unsettled query: the first pass lets through whatever reaches ``threshold - (epsilon +
+rerank_rounding)``, which no row of the answer can lie below, and the rerank's kernel decides the rest.
+
 No CPU compute path: the host moves arrays, decides which queries are settled from three numbers per query, and keeps counts.
 """
 
@@ -27,7 +31,8 @@ import numpy as np
 from . import _native
 from .similarity import _on_device, _raise_for_status, corpus_entry, cosine_scores_device, topk_desc_device
 
-__all__ = ["exact_top_k", "settled", "choose_window", "rerank_rounding", "scan_epsilon", "scan_max_window", "scan_windows"]
+__all__ = ["exact_top_k", "exact_above", "settled", "choose_window", "rerank_rounding", "scan_epsilon", "scan_max_window",
+           "scan_windows", "scan_above", "above_bars", "above_recall"]
 
 METHODS = ("auto", "scan", "gather")
 # (query, live row) pairs of one chunk of the gather.  Per pair: 4 B of score, 8 B of candidate row, 1 B of status, and up to
@@ -35,6 +40,8 @@ METHODS = ("auto", "scan", "gather")
 _GATHER_MAX_PAIRS = 1 << 25
 _SCAN_MAX_DIM = 16384               # what lshrs_scan_topk_* and lshrs_cosine_* take
 _SCAN_MAX_ROWS = (1 << 31) - 1
+# slots of the range search's first launch: max(this, 64 per query) pairs of 16 bytes; more pairs than that cost a second launch
+_ABOVE_FIRST_CAPACITY = 1 << 20
 
 
 def scan_max_window() -> int:
@@ -246,3 +253,209 @@ def exact_top_k(queries, corpus, k: int, *, row_ids=None, method: str = "auto", 
     if return_tensors:
         return ids, scores
     return ids.cpu().numpy(), scores.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------
+# range search: every live row at or above a cosine threshold
+# ------------------------------------------------------------------------------------------
+def _check_above_args(q: int, threshold, max_pairs) -> np.ndarray:
+    """The thresholds of ``q`` queries as float64 ``(q,)``; ``ValueError`` for what ``exact_above`` does not take.  Pure host."""
+    if int(max_pairs) < 0:
+        raise ValueError(f"max_pairs must be >= 0; received {max_pairs}")
+    try:
+        t = np.asarray(threshold, dtype=np.float64)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"threshold must be a number or an array of shape ({q},)") from exc
+    if t.ndim == 0:
+        t = np.full(q, float(t), dtype=np.float64)
+    elif t.shape != (q,):
+        raise ValueError(f"threshold must be a scalar or have shape ({q},); received {t.shape}")
+    if not np.all(np.isfinite(t)) or np.any(t < -1.0) or np.any(t > 1.0):
+        raise ValueError("threshold must be finite and within [-1, 1]")
+    return t
+
+
+def above_bars(thresholds, margin: float) -> np.ndarray:
+    """The first pass's bars (float32) for float64 ``thresholds``: ``t - margin`` evaluated in float64 and rounded DOWN to
+    float32, where ``t`` is the lower of the threshold and its float32 value (the answer is defined by the latter).  A row
+    whose rerank score reaches ``float32(threshold)`` has a cosine of at least ``t - rerank_rounding`` and an approximate score
+    of at least ``t - rerank_rounding - epsilon``: with ``margin`` their sum, it is at or above its bar."""
+    t = np.asarray(thresholds, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        t = np.minimum(t, t.astype(np.float32).astype(np.float64))
+    want = t - float(margin)
+    bars = want.astype(np.float32)
+    high = bars.astype(np.float64) > want
+    bars[high] = np.nextafter(bars[high], np.float32(-np.inf))
+    return bars
+
+
+def scan_above(corpus, queries, bars, capacity: int, row_ids=None):
+    """Device-level entry of the range search's first pass (``lshrs_scan_above_*``): ``corpus`` / ``queries`` / ``row_ids`` as
+    :func:`scan_windows` takes them, ``bars`` float32 ``(q,)`` on the device.  Returns ``(query (capacity,) int32, row
+    (capacity,) int64, approx (capacity,) float32, total uint64-as-int64[1], err int32[1])``: the first ``min(total,
+    capacity)`` slots are pairs, in no particular order; ``total`` counts every pair that reached its bar."""
+    torch = _native.require_gpu()
+    lib = _native.load()
+    entry = corpus_entry(corpus, "ragged").replace("lshrs_cosine_ragged_", "lshrs_scan_above_")
+    dev = corpus.device
+    q, m, dim = int(queries.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
+    capacity = int(capacity)
+    out_q = torch.empty((capacity,), dtype=torch.int32, device=dev)
+    out_row = torch.empty((capacity,), dtype=torch.int64, device=dev)
+    out_approx = torch.empty((capacity,), dtype=torch.float32, device=dev)
+    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    if q == 0:
+        return out_q, out_row, out_approx, total, err
+    nbytes = int(lib.lshrs_scan_above_workspace_bytes(q, m, dim))
+    if nbytes < 0:
+        _native.check(nbytes, "lshrs_scan_above_workspace_bytes")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim,
+                                          row_ids.data_ptr() if row_ids is not None else None, queries.data_ptr(), q,
+                                          bars.data_ptr(), capacity, out_q.data_ptr() if capacity else None,
+                                          out_row.data_ptr() if capacity else None, out_approx.data_ptr() if capacity else None,
+                                          total.data_ptr(), ws.data_ptr(), err.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream), entry)
+    return out_q, out_row, out_approx, total, err
+
+
+def exact_above(queries, corpus, threshold, *, row_ids=None, max_pairs: int = 1 << 26, return_tensors: bool = False,
+                stats: Optional[Dict] = None):
+    """Every row of ``corpus`` at or above a cosine ``threshold`` for every query, exactly: ``(ids (total,) int64, scores
+    (total,) float32, bounds (q + 1,) int64)`` - query ``i`` owns ``[bounds[i], bounds[i + 1])``, scores descending, equal scores
+    by ascending id (the triple ``LSHRS.query_many(return_arrays=True)`` returns); NumPy arrays, or device tensors with
+    ``return_tensors``.
+
+    ``queries``, ``corpus``, ``row_ids``: as :func:`exact_top_k` takes them.  ``threshold``: a number, or one per query
+    (shape ``(q,)``); finite and within [-1, 1], else ``ValueError`` before anything touches the GPU.  The answer of a query
+    is the set of live rows whose RERANK score of that (query, row) - the float32 ``lshrs_cosine_ragged_*`` produces, which is
+    the score returned - satisfies ``score >= float32(threshold)``; no more, no fewer.
+
+    One pass over the rows on the matrix cores (``lshrs_scan_above_*``) emits every pair whose approximate score reaches
+    :func:`above_bars` ``(threshold, scan_epsilon + rerank_rounding)``; the pairs are grouped by query, rescored by the
+    rerank's kernel, cut at the threshold and ordered, all on the device.  One number crosses to the host: how many pairs the
+    pass found.  Beyond ``max(2^20, 64 q)`` of them the pass runs a second time with room for all; beyond ``max_pairs`` the
+    call raises ``ValueError`` without allocating for them.
+    ``stats``: a dict that receives ``queries``, ``emitted`` (pairs the first pass let through), ``kept``, ``launches`` (1 or
+    2) and ``epsilon``.
+
+    A query or a live row of zero norm raises ``ValueError("Cannot normalize zero vector")``; rows beyond the kernels raise
+    the ``NativeLibraryError`` :func:`exact_top_k` raises."""
+    shape = tuple(int(v) for v in getattr(queries, "shape", ())) or tuple(np.asarray(queries).shape)
+    if len(shape) != 2:
+        raise ValueError(f"queries must have shape (q, dim); received {shape}")
+    max_pairs = int(max_pairs)
+    thr64 = _check_above_args(shape[0], threshold, max_pairs)
+    torch = _native.require_gpu()
+    lib = _native.load()
+    corpus_entry(corpus, "ragged")
+    dev = corpus.device
+    with torch.cuda.device(dev):
+        d_q = _on_device(torch, queries, np.float32)
+        if d_q.dim() != 2 or int(d_q.shape[1]) != int(corpus.shape[1]):
+            raise ValueError(f"queries must have shape (q, {int(corpus.shape[1])}); received {tuple(d_q.shape)}")
+        d_q = d_q.to(device=dev, dtype=torch.float32).contiguous()
+        q, m, dim = int(d_q.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
+        if dim > _SCAN_MAX_DIM or m > _SCAN_MAX_ROWS:
+            raise _native.NativeLibraryError(f"exact_above: shape outside kernel limits (LSHRS_E_TOOLARGE): {m} rows of {dim} "
+                                             f"elements; at most {_SCAN_MAX_ROWS} rows of {_SCAN_MAX_DIM}")
+        d_ids = None
+        if row_ids is not None:
+            d_ids = _on_device(torch, row_ids, np.int64).to(device=dev, dtype=torch.int64).contiguous()
+            if d_ids.dim() != 1 or int(d_ids.shape[0]) != m:
+                raise ValueError(f"row_ids must have shape ({m},); received {tuple(d_ids.shape)}")
+        eps = scan_epsilon(corpus.dtype, dim)
+        out = {"queries": q, "emitted": 0, "kept": 0, "launches": 0, "epsilon": eps}
+        ids = torch.empty((0,), dtype=torch.int64, device=dev)
+        scores = torch.empty((0,), dtype=torch.float32, device=dev)
+        bounds = torch.zeros((q + 1,), dtype=torch.int64, device=dev)
+        if q and m:
+            bars = torch.from_numpy(above_bars(thr64, eps + rerank_rounding(dim))).to(dev)
+            t32 = torch.from_numpy(thr64.astype(np.float32)).to(dev)
+            capacity = min(max(_ABOVE_FIRST_CAPACITY, 64 * q), max_pairs)
+            pq, prow, _, total, err = scan_above(corpus, d_q, bars, capacity, d_ids)
+            emitted = int(total.item())                 # (the one size that crosses to the host)
+            out["launches"] = 1
+            if int(err.item()) & 5:
+                raise ValueError("Cannot normalize zero vector")
+            if emitted > max_pairs:
+                raise ValueError(f"exact_above: {emitted} pairs reach the threshold's bar, more than max_pairs = {max_pairs}")
+            if emitted > capacity:
+                del pq, prow
+                pq, prow, _, total, err = scan_above(corpus, d_q, bars, emitted, d_ids)
+                out["launches"] = 2
+                if int(total.item()) != emitted:        # (the same launch on the same data: the same count)
+                    raise RuntimeError("exact_above: the second pass counted other pairs than the first")
+            out["emitted"] = emitted
+            if emitted:
+                # by query (stable), then the rerank's own score of every pair: its lists are the queries' runs
+                pq, by_q = torch.sort(pq[:emitted].long(), stable=True)
+                prow = prow[:emitted][by_q].contiguous()
+                count = torch.bincount(pq, minlength=q)
+                off = (torch.cumsum(count, 0) - count).contiguous()
+                exact = torch.empty((emitted,), dtype=torch.float32, device=dev)
+                err2 = torch.zeros(1, dtype=torch.int32, device=dev)
+                entry = corpus_entry(corpus, "ragged")
+                cnt32 = count.to(torch.int32)
+                _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim, d_q.data_ptr(), q,
+                                                  prow.data_ptr(), off.data_ptr(), cnt32.data_ptr(), emitted, exact.data_ptr(),
+                                                  err2.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), entry)
+                if int(err2.item()) & 5:
+                    raise ValueError("Cannot normalize zero vector")
+                keep = exact >= t32[pq]                 # (a NaN is not kept)
+                pq, exact = pq[keep], exact[keep]
+                pid = prow[keep] if d_ids is None else d_ids[prow[keep]]
+                # what is left is still grouped by query.  Ascending id first; then ONE stable sort on {query, an integer that
+                # descends with the score (-0.0 with 0.0)} orders every query's run by descending score, ties by the id order
+                _, order = torch.sort(pid, stable=True)
+                pq, exact, pid = pq[order], exact[order], pid[order]
+                bits = (exact + 0.0).view(torch.int32)
+                down = 0x7FFFFFFF - torch.where(bits >= 0, bits, bits ^ 0x7FFFFFFF).long()     # in [0, 2^32)
+                _, order = torch.sort((pq << 32) | down, stable=True)
+                pq, exact, pid = pq[order], exact[order], pid[order]
+                ids, scores = pid.contiguous(), exact.contiguous()
+                bounds[1:] = torch.cumsum(torch.bincount(pq, minlength=q), 0)
+                out["kept"] = int(ids.shape[0])
+    if stats is not None:
+        stats.clear()
+        stats.update(out)
+    if return_tensors:
+        return ids, scores, bounds
+    return ids.cpu().numpy(), scores.cpu().numpy(), bounds.cpu().numpy()
+
+
+def above_recall(truth_ids, truth_scores, truth_bounds, cand_ids, cand_bounds, num_bands: int, rows_per_band: int) -> Dict:
+    """The bookkeeping of ``LSHRS.recall_above``, on host arrays: the truth (ids, scores, bounds of :func:`exact_above`) against
+    candidate lists (ids, bounds; every id at most once per query).  Returns ``recall`` (truth pairs that are candidates /
+    truth pairs, pooled over the queries; 1.0 when there is no truth), ``per_query`` (float32, NaN where a query has no
+    truth), ``truth_pairs``, ``candidates`` (mean list length), ``precision`` (share of the candidate pairs that are truth; 1.0
+    when there is no candidate) and ``expected``: the mean over the truth pairs of ``1 - (1 - p^r)^b`` with ``p = 1 -
+    acos(s) / pi``, the chance that sign random projections put a pair of cosine ``s`` into one bucket of at least one of
+    ``b = num_bands`` bands of ``r = rows_per_band`` bits (NaN when there is no truth)."""
+    truth_ids = np.asarray(truth_ids, dtype=np.int64)
+    truth_scores = np.asarray(truth_scores, dtype=np.float64)
+    truth_bounds = np.asarray(truth_bounds, dtype=np.int64)
+    cand_ids = np.asarray(cand_ids, dtype=np.int64)
+    cand_bounds = np.asarray(cand_bounds, dtype=np.int64)
+    n = int(truth_bounds.shape[0]) - 1
+    if int(cand_bounds.shape[0]) - 1 != n:
+        raise ValueError("truth and candidates must cover the same queries")
+    per = np.full(n, np.nan, dtype=np.float32)
+    found = 0
+    for i in range(n):
+        mine = truth_ids[truth_bounds[i]:truth_bounds[i + 1]]
+        if mine.shape[0]:
+            hit = np.intersect1d(mine, cand_ids[cand_bounds[i]:cand_bounds[i + 1]]).shape[0]
+            found += hit
+            per[i] = hit / mine.shape[0]
+    truth_pairs, cand_pairs = int(truth_ids.shape[0]), int(cand_ids.shape[0])
+    expected = float("nan")
+    if truth_pairs:
+        p = 1.0 - np.arccos(np.clip(truth_scores, -1.0, 1.0)) / np.pi
+        expected = float(np.mean(1.0 - (1.0 - p ** int(rows_per_band)) ** int(num_bands)))
+    return {"recall": found / truth_pairs if truth_pairs else 1.0, "per_query": per, "truth_pairs": truth_pairs,
+            "candidates": cand_pairs / n if n else 0.0, "precision": found / cand_pairs if cand_pairs else 1.0,
+            "expected": expected}

@@ -221,6 +221,12 @@ def _declare(lib: ctypes.CDLL) -> None:
     for dt in SCAN_ELEMS:
         scan = getattr(lib, "lshrs_scan_topk_" + dt)
         scan.argtypes, scan.restype = [vp, i64, i64, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp], c.c_int
+    lib.lshrs_scan_above_workspace_bytes.argtypes = [i32, i64, i32]
+    lib.lshrs_scan_above_workspace_bytes.restype = i64
+    # (corpus, m, ldc, dim, row_ids, queries, q, bars, capacity, out_query, out_row, out_approx, total, workspace, err, stream)
+    for dt in SCAN_ELEMS:
+        above = getattr(lib, "lshrs_scan_above_" + dt)
+        above.argtypes, above.restype = [vp, i64, i64, i32, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp], c.c_int
     lib.lshrs_pipe_create.argtypes = [i32, i32, i32, i32, i32]
     lib.lshrs_pipe_create.restype = vp
     lib.lshrs_pipe_destroy.argtypes = [vp]
@@ -289,6 +295,12 @@ EXPORTS = (
     "lshrs_scan_topk_f16",
     "lshrs_scan_topk_i8",
     "lshrs_scan_topk_f8e4m3",
+    "lshrs_scan_above_workspace_bytes",
+    "lshrs_scan_above_f32",
+    "lshrs_scan_above_bf16",
+    "lshrs_scan_above_f16",
+    "lshrs_scan_above_i8",
+    "lshrs_scan_above_f8e4m3",
     "lshrs_pipe_create",
     "lshrs_pipe_destroy",
     "lshrs_pipe_hash_f32",

@@ -659,6 +659,54 @@ class LSHRS:
         return {"recall": float(per.mean()) if n else 0.0, "per_query": per, "exact": exact,
                 "returned": float(np.diff(bounds).mean()) if n else 0.0}
 
+    def search_exact_above(self, vectors, threshold, *, return_arrays: bool = False):
+        """Every indexed vector at or above a cosine ``threshold`` (a number, or one per query) for every query, EXACTLY: the
+        range-search counterpart of :meth:`search_exact`, over the same corpus (``lshrs_amd.exact_above``) and with the same
+        errors where there is none.  Returns per query ``[(id, score), ...]``, scores descending and equal scores by ascending
+        id - or ``(ids, scores, bounds)`` as :meth:`query_many` returns them with ``return_arrays``.  ``last_search_stats``
+        tells what the call did."""
+        resident = _device_tensor(vectors)
+        arr = resident if resident is not None else np.asarray(vectors, dtype=np.float32)
+        if len(arr.shape) != 2 or int(arr.shape[1]) != self._dim:
+            raise ValueError(f"Vectors must have shape (n, {self._dim}); received {tuple(arr.shape)}")
+        if resident is not None:
+            arr = resident.float()
+        corpus = self._rerank_corpus()
+        if corpus is None:
+            self._require_vector_fetch_fn()
+            raise RuntimeError("search_exact_above needs the indexed vectors on the device: set_corpus(...) or keep_vectors=...")
+        if isinstance(corpus, DeviceVectors):
+            ids, scores, bounds = corpus.search_above(arr, threshold)
+            self.last_search_stats = dict(corpus.last_search_stats)
+        else:
+            from . import _query_device as qd
+            from ._exact import exact_above
+
+            stats: Dict[str, Any] = {}
+            table = qd.corpus_on(corpus, getattr(corpus, "device", None) if _device_tensor(corpus) is not None
+                                 else self._hasher._torch_device(), self._dim)
+            ids, scores, bounds = exact_above(arr, table, threshold, stats=stats)
+            self.last_search_stats = stats
+        if return_arrays:
+            return ids, scores, bounds
+        with _gc_paused():
+            return qh.split_rows(list(zip(ids.tolist(), scores.astype(np.float64).tolist())), np.diff(bounds))
+
+    def recall_above(self, vectors, threshold) -> Dict[str, Any]:
+        """What the index finds of the pairs it is configured for, measured: the truth is :meth:`search_exact_above`
+        ``(vectors, threshold)``, the candidates are :meth:`query_many` ``(vectors, top_k=None)`` - every id that shares a
+        bucket with the query.  Returns ``recall`` (truth pairs among the candidates / truth pairs, pooled over the queries;
+        1.0 when there are none), ``per_query`` (float32, NaN where a query has no truth), ``truth_pairs``, ``candidates``
+        (mean list length), ``precision`` (share of the candidate pairs that are truth) and ``expected``: the mean over the
+        truth pairs of ``1 - (1 - p^r)^b`` with ``p = 1 - acos(s) / pi``, the collision law of this hasher's sign random
+        projections (``lshrs_amd._exact.above_recall``).  The measured counterpart of ``get_optimal_config``."""
+        from ._exact import above_recall
+
+        t_ids, t_scores, t_bounds = self.search_exact_above(vectors, threshold, return_arrays=True)
+        cand_ids, _, cand_bounds = self.query_many(vectors, top_k=None, return_arrays=True)
+        return above_recall(t_ids, t_scores, t_bounds, cand_ids, cand_bounds, self._config["num_bands"],
+                            self._config["rows_per_band"])
+
     def _query_many_device(self, arr, top_k, top_p, corpus):
         """``query_many`` with everything between the upload of the queries and the download of the answers on the device."""
         from . import _native

@@ -18,6 +18,8 @@
 // query); when a buffer is full the workgroup prunes it to its `window` largest by rank counting (items in registers, handed
 // round the wave by v_readlane) and raises the threshold.  Each slice leaves its sorted winners in the workspace;
 // scan_merge_kernel orders the slices' winners of a query in LDS.  No global atomics but the error bits.
+// Range scan (scan_above_kernel, lshrs_scan_above_*): the same first pass with no selection at all - every (query, live row)
+// whose approximate score reaches the query's bar is emitted to flat arrays through one global cursor (lshrs_amd.exact_above).
 // ABI and reference citations: include/lshrs_hip.h.  Design notes, the epsilon derivation and the roof: DESIGN.md.
 #include "lshrs_common.h"
 
@@ -442,6 +444,176 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
 }
 
 // ------------------------------------------------------------------------------------------
+// one pass of a workgroup: 256 rows from `base` (64 per wave, two 32-row tiles) against the query tile's image, all chunks of k.
+// Leaves acc[t][cb] (the dot products of tile t with column block cb), nn[t] (this lane's half of ||row||^2), live[t] and
+// row0[t] (the tile's first row).  Every thread of the workgroup calls it (it synchronises on the B chunk in LDS, `bl`).
+// A copy of scan_kernel's main loop, statement for statement: calling this from scan_kernel moved its register allocation
+// (spills and scratch of seven of its ten instantiations), so that kernel keeps its loop inline and the two are kept alike by hand.
+// ------------------------------------------------------------------------------------------
+template <typename E, bool ALIGNED>
+__device__ __forceinline__ void scan_pass(const typename ScanElem<E>::T* __restrict__ corpus, int64_t ldc, int dim, int nchunks,
+                                          const int64_t* __restrict__ row_ids, const u32x4* __restrict__ bimg, u32x4* bl,
+                                          int64_t base, int64_t row_begin, int64_t row_end, int tid, bool (&live)[2],
+                                          int64_t (&row0)[2], f32x16 (&acc)[2][2], float (&nn)[2]) {
+  using T = typename ScanElem<E>::T;
+  constexpr bool kTwo = ScanElem<E>::kTerms == 2;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const T* rowp[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    row0[t] = base + wave * 64 + t * 32;
+    const int64_t row = row0[t] + r;
+    const bool valid = row < row_end;
+    live[t] = valid && (row_ids == nullptr || row_ids[row] >= 0);
+    rowp[t] = corpus + (valid ? row : row_begin) * ldc;      // (a row past the end reads the slice's first row, unused)
+  }
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[t][cb][i] = 0.f;
+  nn[0] = nn[1] = 0.f;
+
+  // chunk c + 1's rows and B fragments are asked for before chunk c is multiplied, so that the loads fly under the MFMAs
+  auto load_chunk = [&](int c, ScanRaw<E> (&raw)[2], u32x4 (&bst)[4]) {
+    const int k0 = c * kScanKChunk + 32 * h;
+    if (ALIGNED && (c + 1) * kScanKChunk <= dim) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) raw[t] = scan_load_vec<E>(rowp[t] + k0);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) raw[t] = scan_load_elems<E>(rowp[t], k0, dim);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bst[i] = bimg[(int64_t)c * (kScanChunkBytes / 16) + i * kScanThreads + tid];
+  };
+  // (one-term rows only: a two-term row's fragments leave no registers for a second chunk)
+  constexpr bool kAhead = !kTwo;
+  ScanRaw<E> nraw[2];
+  u32x4 nbst[4];
+  if constexpr (kAhead) load_chunk(0, nraw, nbst);
+  for (int c = 0; c < nchunks; ++c) {
+    if constexpr (!kAhead) load_chunk(c, nraw, nbst);
+    ScanRaw<E> raw[2] = {nraw[0], nraw[1]};
+    __syncthreads();                    // the last chunk's fragments have been read
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bl[i * kScanThreads + tid] = nbst[i];
+    __syncthreads();
+    if constexpr (kAhead)
+      if (c + 1 < nchunks) load_chunk(c + 1, nraw, nbst);
+
+    u32x4 ahi[2][4], amid[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) scan_fragments<E>(raw[t], ahi[t], amid[t], nn[t]);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        const bf16x8 bh = __builtin_bit_cast(bf16x8, bl[((0 * 4 + s) * 2 + cb) * 64 + lane]);
+        const bf16x8 bm = __builtin_bit_cast(bf16x8, bl[((1 * 4 + s) * 2 + cb) * 64 + lane]);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const bf16x8 ah = __builtin_bit_cast(bf16x8, ahi[t][s]);
+          acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t][cb], 0, 0, 0);
+          acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[t][cb], 0, 0, 0);
+          if constexpr (kTwo)
+            acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, amid[t][s]), bh, acc[t][cb], 0, 0, 0);
+        }
+      }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// range scan: the same grid, image and pass; instead of a window per query, EVERY (query, live row) whose approximate score
+// reaches the query's bar goes out.  A wave that has hits in a 32-row tile reserves their slots with one 64-bit atomicAdd on
+// the global cursor `total` (which counts every hit, also those beyond `capacity`: the caller then knows what to allocate) and
+// writes those that fit.  Order unspecified.  LDS: the B chunk only.
+// ------------------------------------------------------------------------------------------
+template <typename E, bool ALIGNED>
+__global__ __launch_bounds__(kScanThreads, 2) void scan_above_kernel(const typename ScanElem<E>::T* __restrict__ corpus, int64_t m,
+                                                                  int64_t ldc, int dim, const int64_t* __restrict__ row_ids,
+                                                                  const u32x4* __restrict__ image,
+                                                                  const float* __restrict__ qnorm, const float* __restrict__ bars,
+                                                                  int q, int64_t rows_per_slice, int64_t capacity,
+                                                                  int32_t* __restrict__ out_query, int64_t* __restrict__ out_row,
+                                                                  float* __restrict__ out_approx,
+                                                                  unsigned long long* __restrict__ total,
+                                                                  int32_t* __restrict__ err) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char scan_lds[];
+  u32x4* bl = reinterpret_cast<u32x4*>(scan_lds);
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int r = lane & 31, h = lane >> 5;
+  const int slice = blockIdx.x, qtile = blockIdx.y;
+  const int nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
+  const int64_t row_begin = (int64_t)slice * rows_per_slice;
+  const int64_t row_end = min(m, row_begin + rows_per_slice);
+  const u32x4* bimg = image + (int64_t)qtile * nchunks * (kScanChunkBytes / 16);
+
+  float qn[2], bar[2];
+  int qi[2];
+#pragma unroll
+  for (int cb = 0; cb < 2; ++cb) {
+    qi[cb] = qtile * kScanQTile + cb * 32 + r;
+    qn[cb] = qnorm[qi[cb]];               // (padded to whole tiles)
+    bar[cb] = qi[cb] < q ? bars[qi[cb]] : __builtin_inff();   // (nothing reaches the bar of a padding query, NaN reaches none)
+  }
+
+  for (int64_t base = row_begin; base < row_end; base += kScanPassRows) {
+    bool live[2];
+    int64_t row0[2];
+    f32x16 acc[2][2];
+    float nn[2];
+    scan_pass<E, ALIGNED>(corpus, ldc, dim, nchunks, row_ids, bimg, bl, base, row_begin, row_end, tid, live, row0, acc, nn);
+
+    // the finished 256 x 64 tile: acc[t][cb][i] is row (i & 3) + 8 (i >> 2) + 4 h of tile t, query cb * 32 + r
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      nn[t] += __shfl_xor(nn[t], 32);
+      const float xn = sqrtf(nn[t]);
+      if (live[t] && xn == 0.f && h == 0 && err != nullptr) atomicOr(err, 1);
+      const uint32_t livemask = (uint32_t)__ballot(live[t]);
+      uint32_t hits = 0;                  // bit cb * 16 + i
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int rr = (i & 3) + 8 * (i >> 2) + 4 * h;
+          const float rn = __shfl(xn, rr);
+          const float sc = acc[t][cb][i] / (rn * qn[cb]);
+          acc[t][cb][i] = sc;
+          if (((livemask >> rr) & 1u) && sc >= bar[cb]) hits |= 1u << (cb * 16 + i);
+        }
+      if (__ballot(hits != 0) == 0ull) continue;        // (the common case: nothing of this tile reaches a bar)
+      const int mine = __popc(hits);
+      int incl = mine;                    // inclusive prefix sum of the lanes' hit counts
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
+      }
+      unsigned long long first = 0ull;
+      if (lane == 63) first = atomicAdd(total, (unsigned long long)incl);     // (lane 63's sum is the wave's)
+      int64_t slot = (int64_t)__shfl(first, 63) + (incl - mine);
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (hits & (1u << (cb * 16 + i))) {
+            if (slot < capacity) {
+              out_query[slot] = qi[cb];
+              out_row[slot] = row0[t] + (i & 3) + 8 * (i >> 2) + 4 * h;
+              out_approx[slot] = acc[t][cb][i];
+            }
+            ++slot;
+          }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // one workgroup per query: the slices' winners into LDS, bitonic network descending, the first `window` out
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kScanThreads) void scan_merge_kernel(const uint64_t* __restrict__ parts, int n, int npad, int window,
@@ -489,6 +661,23 @@ struct ScanPlan {
   int64_t image_bytes, qnorm_bytes, parts_bytes;
 };
 
+// slices: one round of the workgroups that are resident at a time - 256 CUs, two per CU while their LDS (`lds` bytes) fits twice
+// into the CU's 160 KiB, else one - over all query tiles: a second, part-filled round costs a whole slice's time.  At least
+// 1024 rows each, and no more than `limit` (scan_kernel: what one merge workgroup sorts in LDS).
+inline void scan_slices(int64_t m, int qtiles, int64_t lds, int64_t limit, int64_t& rows_per_slice, int& slices) {
+  const int64_t resident = 256 * (2 * lds <= 160 * 1024 ? 2 : 1);
+  const int64_t qt = qtiles > 0 ? qtiles : 1;
+  int64_t want = resident / qt;
+  const int64_t by_rows = (m + 1023) / 1024;
+  if (want > by_rows) want = by_rows;
+  if (want > limit) want = limit;
+  if (want < 1) want = 1;
+  const int64_t passes = (m + kScanPassRows - 1) / kScanPassRows;
+  const int64_t rps = (passes + want - 1) / want * kScanPassRows;
+  rows_per_slice = rps;
+  slices = (int)((m + rps - 1) / rps);
+}
+
 inline int scan_plan(int32_t q, int64_t m, int32_t dim, int32_t window, ScanPlan& p) {
   if (q < 0 || m <= 0 || dim <= 0 || window <= 0 || window > kScanMaxWindow) return LSHRS_E_BADARG;
   if (dim > kScanMaxDim || m > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
@@ -497,21 +686,8 @@ inline int scan_plan(int32_t q, int64_t m, int32_t dim, int32_t window, ScanPlan
   p.nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
   p.cap = 64;
   while (p.cap < 2 * window) p.cap <<= 1;
-  // slices: one round of the workgroups that are resident at a time - 256 CUs, two per CU while their LDS fits twice into the
-  // CU's 160 KiB, else one - over all query tiles: a second, part-filled round costs a whole slice's time.  At least 1024
-  // rows each, and no more than one merge workgroup sorts in LDS.
   const int64_t lds = (int64_t)kScanChunkBytes + (int64_t)kScanQTile * p.cap * 8 + kScanQTile * 12;
-  const int64_t resident = 256 * (2 * lds <= 160 * 1024 ? 2 : 1);
-  const int64_t qt = p.qtiles > 0 ? p.qtiles : 1;
-  int64_t want = resident / qt;
-  const int64_t by_rows = (m + 1023) / 1024;
-  if (want > by_rows) want = by_rows;
-  if (want > kScanMergeItems / window) want = kScanMergeItems / window;
-  if (want < 1) want = 1;
-  const int64_t passes = (m + kScanPassRows - 1) / kScanPassRows;
-  const int64_t rps = (passes + want - 1) / want * kScanPassRows;
-  p.rows_per_slice = rps;
-  p.slices = (int)((m + rps - 1) / rps);
+  scan_slices(m, p.qtiles, lds, kScanMergeItems / window, p.rows_per_slice, p.slices);
   p.image_bytes = (int64_t)p.qtiles * p.nchunks * kScanChunkBytes;
   p.qnorm_bytes = (int64_t)p.qtiles * kScanQTile * (int64_t)sizeof(float);
   p.parts_bytes = (int64_t)q * p.slices * window * (int64_t)sizeof(uint64_t);
@@ -572,6 +748,59 @@ int scan_topk(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int
                      out_approx, out_count);
   return -(int)hipGetLastError();
 }
+
+// ---- range scan: geometry without the merge limit, residency from scan_above_kernel's own LDS (the B chunk) ----
+inline int scan_above_plan(int32_t q, int64_t m, int32_t dim, ScanPlan& p) {
+  if (q < 0 || m <= 0 || dim <= 0) return LSHRS_E_BADARG;
+  if (dim > kScanMaxDim || m > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
+  p.qtiles = (q + kScanQTile - 1) / kScanQTile;
+  if (p.qtiles > 65535) return LSHRS_E_TOOLARGE;
+  p.nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
+  p.cap = 0;
+  scan_slices(m, p.qtiles, kScanChunkBytes, INT64_MAX, p.rows_per_slice, p.slices);
+  p.image_bytes = (int64_t)p.qtiles * p.nchunks * kScanChunkBytes;
+  p.qnorm_bytes = (int64_t)p.qtiles * kScanQTile * (int64_t)sizeof(float);
+  p.parts_bytes = 0;
+  return 0;
+}
+
+template <typename E>
+int scan_above(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids,
+               const float* queries, int32_t q, const float* bars, int64_t capacity, int32_t* out_query, int64_t* out_row,
+               float* out_approx, uint64_t* total, void* workspace, int32_t* err, void* stream) {
+  if (q == 0) return 0;
+  ScanPlan p;
+  const int bad = scan_above_plan(q, m, dim, p);
+  if (bad) return bad;
+  const auto addr = [](const void* ptr) { return reinterpret_cast<uintptr_t>(ptr); };
+  if (corpus == nullptr || queries == nullptr || bars == nullptr || total == nullptr || workspace == nullptr || capacity < 0 ||
+      (capacity > 0 && (out_query == nullptr || out_row == nullptr || out_approx == nullptr)) || (addr(workspace) & 15) ||
+      (addr(total) & 7) || (addr(out_row) & 7) || (addr(out_query) & 3) || (addr(out_approx) & 3) || (addr(bars) & 3) ||
+      (addr(queries) & 3) || ldc < dim)
+    return LSHRS_E_BADARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  u32x4* image = reinterpret_cast<u32x4*>(ws);
+  float* qnorm = reinterpret_cast<float*>(ws + p.image_bytes);
+  const int qpad = p.qtiles * kScanQTile;
+  const hipError_t e = hipMemsetAsync(total, 0, sizeof(uint64_t), s);
+  if (e != hipSuccess) return -(int)e;
+  hipLaunchKernelGGL(scan_prep_kernel, dim3((unsigned)p.nchunks, (unsigned)p.qtiles), dim3(kScanThreads), 0, s, queries, q, dim,
+                     p.nchunks, image);
+  hipLaunchKernelGGL(scan_qnorm_kernel, dim3((unsigned)(qpad / kScanWaves)), dim3(kScanThreads), 0, s, queries, q, qpad, dim,
+                     qnorm, err);
+  constexpr int kAlign = ScanElem<E>::kAlign;
+  const bool aligned = (ldc % kAlign == 0) && ((addr(corpus) & 15) == 0);
+  const dim3 grid((unsigned)p.slices, (unsigned)p.qtiles), block(kScanThreads);
+  unsigned long long* cursor = reinterpret_cast<unsigned long long*>(total);
+  if (aligned)
+    hipLaunchKernelGGL((scan_above_kernel<E, true>), grid, block, (size_t)kScanChunkBytes, s, corpus, m, ldc, dim, row_ids, image,
+                       qnorm, bars, q, p.rows_per_slice, capacity, out_query, out_row, out_approx, cursor, err);
+  else
+    hipLaunchKernelGGL((scan_above_kernel<E, false>), grid, block, (size_t)kScanChunkBytes, s, corpus, m, ldc, dim, row_ids, image,
+                       qnorm, bars, q, p.rows_per_slice, capacity, out_query, out_row, out_approx, cursor, err);
+  return -(int)hipGetLastError();
+}
 }  // namespace
 
 extern "C" {
@@ -624,6 +853,48 @@ int lshrs_scan_topk_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_
                            const float* queries, int32_t q, int32_t window, int64_t* out_rows, float* out_approx,
                            int32_t* out_count, void* workspace, int32_t* err, void* stream) {
   return scan_topk<F8E4M3>(corpus, m, ldc, dim, row_ids, queries, q, window, out_rows, out_approx, out_count, workspace, err, stream);
+}
+
+int64_t lshrs_scan_above_workspace_bytes(int32_t q, int64_t m, int32_t dim) {
+  ScanPlan p;
+  const int bad = scan_above_plan(q, m, dim, p);
+  if (bad) return bad;
+  return p.image_bytes + p.qnorm_bytes + 16;
+}
+
+int lshrs_scan_above_f32(const float* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, const float* queries,
+                         int32_t q, const float* bars, int64_t capacity, int32_t* out_query, int64_t* out_row, float* out_approx,
+                         uint64_t* total, void* workspace, int32_t* err, void* stream) {
+  return scan_above<float>(corpus, m, ldc, dim, row_ids, queries, q, bars, capacity, out_query, out_row, out_approx, total, workspace,
+                        err, stream);
+}
+
+int lshrs_scan_above_bf16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, const float* queries,
+                         int32_t q, const float* bars, int64_t capacity, int32_t* out_query, int64_t* out_row, float* out_approx,
+                         uint64_t* total, void* workspace, int32_t* err, void* stream) {
+  return scan_above<Bf16>(corpus, m, ldc, dim, row_ids, queries, q, bars, capacity, out_query, out_row, out_approx, total, workspace,
+                        err, stream);
+}
+
+int lshrs_scan_above_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, const float* queries,
+                         int32_t q, const float* bars, int64_t capacity, int32_t* out_query, int64_t* out_row, float* out_approx,
+                         uint64_t* total, void* workspace, int32_t* err, void* stream) {
+  return scan_above<F16>(corpus, m, ldc, dim, row_ids, queries, q, bars, capacity, out_query, out_row, out_approx, total, workspace,
+                        err, stream);
+}
+
+int lshrs_scan_above_i8(const int8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, const float* queries,
+                         int32_t q, const float* bars, int64_t capacity, int32_t* out_query, int64_t* out_row, float* out_approx,
+                         uint64_t* total, void* workspace, int32_t* err, void* stream) {
+  return scan_above<I8>(corpus, m, ldc, dim, row_ids, queries, q, bars, capacity, out_query, out_row, out_approx, total, workspace,
+                        err, stream);
+}
+
+int lshrs_scan_above_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, const float* queries,
+                         int32_t q, const float* bars, int64_t capacity, int32_t* out_query, int64_t* out_row, float* out_approx,
+                         uint64_t* total, void* workspace, int32_t* err, void* stream) {
+  return scan_above<F8E4M3>(corpus, m, ldc, dim, row_ids, queries, q, bars, capacity, out_query, out_row, out_approx, total, workspace,
+                        err, stream);
 }
 
 }  // extern "C"

@@ -371,6 +371,23 @@ class DeviceVectors:
         self.last_search_stats = stats
         return got
 
+    def search_above(self, queries, threshold, *, max_pairs: int = 1 << 26, return_tensors: bool = False):
+        """Every stored vector at or above a cosine ``threshold`` (a number, or one per query) for every query, exactly, under
+        the caller's ids: ``(ids (total,) int64, scores (total,) float32, bounds (q + 1,) int64)`` -
+        :func:`lshrs_amd.exact_above` over the row block where it is, superseded and erased rows left out.  What the call did
+        (pairs the first pass let through, pairs kept, launches, epsilon) is left in ``last_search_stats``."""
+        from ._exact import exact_above
+
+        shape = tuple(int(v) for v in getattr(queries, "shape", ())) or tuple(np.asarray(queries).shape)
+        if len(shape) != 2 or shape[1] != self.dim:
+            raise ValueError(f"Vectors must have shape (n, {self.dim}); received {shape}")
+        rows, row_ids = self._search_snapshot()
+        stats: Dict[str, Any] = {}
+        got = exact_above(queries, rows, threshold, row_ids=row_ids, max_pairs=max_pairs, return_tensors=return_tensors,
+                          stats=stats)
+        self.last_search_stats = stats
+        return got
+
     @property
     def rows(self):
         """The ``(rows in use, dim)`` view of the row block."""
