@@ -29,7 +29,8 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import _native
-from .similarity import _on_device, _raise_for_status, corpus_entry, cosine_scores_device, topk_desc_device
+from .similarity import (_CORPUS_ENTRY, _CORPUS_ENTRY_8BIT, _on_device, _raise_for_status, corpus_suffix, cosine_ragged_device,
+                         cosine_scores_device, topk_desc_device)
 
 __all__ = ["exact_top_k", "exact_above", "settled", "choose_window", "rerank_rounding", "scan_epsilon", "scan_max_window",
            "scan_windows", "scan_above", "above_bars", "above_recall"]
@@ -53,10 +54,10 @@ def scan_epsilon(dtype, dim: int) -> float:
     """``lshrs_scan_epsilon``: the proven bound on |approximate score - cosine of the stored row| for rows of ``dtype``
     (a torch dtype or its name) and ``dim`` elements."""
     name = str(dtype).replace("torch.", "")
-    names = {"float32": 0, "bfloat16": 1, "float16": 2, "int8": 3, "float8_e4m3fn": 4}
-    if name not in names:
+    suffix = _CORPUS_ENTRY.get(name, _CORPUS_ENTRY_8BIT.get(name))
+    if suffix is None:
         raise ValueError(f"no scan over rows of {dtype}")
-    eps = float(_native.load().lshrs_scan_epsilon(names[name], int(dim)))
+    eps = float(_native.load().lshrs_scan_epsilon(_native.SCAN_ELEMS.index(suffix), int(dim)))
     if eps < 0:
         raise ValueError(f"lshrs_scan_epsilon takes 1 <= dim <= 16384; received {dim}")
     return eps
@@ -97,13 +98,22 @@ def _check_method(method: str) -> None:
         raise ValueError("method must be 'auto', 'scan' or 'gather'")
 
 
+def _scan_workspace(torch, lib, sizer: str, dev, *shape):
+    """The workspace of a first pass: ``sizer`` (``lshrs_scan_workspace_bytes`` or ``lshrs_scan_above_workspace_bytes``) of
+    ``shape`` bytes on ``dev``; a negative size raises what ``_native.check`` makes of it."""
+    nbytes = int(getattr(lib, sizer)(*shape))
+    if nbytes < 0:
+        _native.check(nbytes, sizer)
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
 def scan_windows(corpus, queries, window: int, row_ids=None):
-    """Device-level entry of the first pass: ``corpus`` (m, dim) as ``corpus_entry`` accepts it, ``queries`` (q, dim) float32
+    """Device-level entry of the first pass: ``corpus`` (m, dim) as ``corpus_suffix`` accepts it, ``queries`` (q, dim) float32
     contiguous on the same device, ``row_ids`` optional int64 (m,) there.  Returns ``(rows (q, window) int64, approx (q, window)
     float32, count (q,) int32, err int32[1])`` as ``lshrs_scan_topk_*`` leaves them."""
     torch = _native.require_gpu()
     lib = _native.load()
-    entry = corpus_entry(corpus, "ragged").replace("lshrs_cosine_ragged_", "lshrs_scan_topk_")
+    entry = "lshrs_scan_topk_" + corpus_suffix(corpus)
     dev = corpus.device
     q, m, dim = int(queries.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
     rows = torch.empty((q, window), dtype=torch.int64, device=dev)
@@ -112,11 +122,8 @@ def scan_windows(corpus, queries, window: int, row_ids=None):
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     if q == 0:
         return rows, approx, count, err
-    nbytes = int(lib.lshrs_scan_workspace_bytes(q, m, dim, window))
-    if nbytes < 0:
-        _native.check(nbytes, "lshrs_scan_workspace_bytes")
     with torch.cuda.device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _scan_workspace(torch, lib, "lshrs_scan_workspace_bytes", dev, q, m, dim, window)
         _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim,
                                           row_ids.data_ptr() if row_ids is not None else None, queries.data_ptr(), q, window,
                                           rows.data_ptr(), approx.data_ptr(), count.data_ptr(), ws.data_ptr(), err.data_ptr(),
@@ -124,20 +131,14 @@ def scan_windows(corpus, queries, window: int, row_ids=None):
     return rows, approx, count, err
 
 
-def _rescore(torch, lib, corpus, queries, rows, count):
+def _rescore(torch, corpus, queries, rows, count):
     """The rerank's score of every (query, window row): ``lshrs_cosine_ragged_*`` over the rows as they stand, ``-inf`` behind
     each query's ``count``."""
-    entry = corpus_entry(corpus, "ragged")
     dev = corpus.device
     q, w = int(rows.shape[0]), int(rows.shape[1])
     scores = torch.full((q, w), float("-inf"), dtype=torch.float32, device=dev)
     off = torch.arange(q, dtype=torch.int64, device=dev) * w
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _native.check(getattr(lib, entry)(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)), int(corpus.shape[1]),
-                                          queries.data_ptr(), q, rows.data_ptr(), off.data_ptr(), count.data_ptr(), q * w,
-                                          scores.data_ptr(), err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), entry)
-    return scores, err
+    return cosine_ragged_device(corpus, queries, rows, off, count, q * w, scores=scores)
 
 
 def _gather(torch, corpus, queries, live_rows, live_ids, kk: int):
@@ -158,6 +159,40 @@ def _gather(torch, corpus, queries, live_rows, live_ids, kk: int):
         ids[lo:hi] = live_ids[order.long()]
         scores[lo:hi] = best
     return ids, scores
+
+
+def _search_args(queries, corpus, row_ids, caller: str):
+    """The opening of ``exact_top_k`` and ``exact_above`` (``caller``: the name their messages carry): the corpus checked
+    (``corpus_suffix``), the queries as a contiguous float32 ``(q, dim)`` tensor on its device, ``row_ids`` as an int64 ``(m,)``
+    one there (or None), the shapes within the kernels' limits.  Returns ``(d_q, d_ids, q, m, dim)``."""
+    torch = _native.require_gpu()
+    _native.load()
+    corpus_suffix(corpus)
+    dev = corpus.device
+    with torch.cuda.device(dev):
+        d_q = _on_device(torch, queries, np.float32)
+        if d_q.dim() != 2 or int(d_q.shape[1]) != int(corpus.shape[1]):
+            raise ValueError(f"queries must have shape (q, {int(corpus.shape[1])}); received {tuple(d_q.shape)}")
+        d_q = d_q.to(device=dev, dtype=torch.float32).contiguous()
+        q, m, dim = int(d_q.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
+        if dim > _SCAN_MAX_DIM or m > _SCAN_MAX_ROWS:
+            # (beyond the scan and beyond the rerank's entries alike: what a rerank of such rows raises, before any launch)
+            raise _native.NativeLibraryError(f"{caller}: shape outside kernel limits (LSHRS_E_TOOLARGE): {m} rows of {dim} "
+                                             f"elements; at most {_SCAN_MAX_ROWS} rows of {_SCAN_MAX_DIM}")
+        d_ids = None
+        if row_ids is not None:
+            d_ids = _on_device(torch, row_ids, np.int64).to(device=dev, dtype=torch.int64).contiguous()
+            if d_ids.dim() != 1 or int(d_ids.shape[0]) != m:
+                raise ValueError(f"row_ids must have shape ({m},); received {tuple(d_ids.shape)}")
+    return d_q, d_ids, q, m, dim
+
+
+def _finish(stats: Optional[Dict], out: Dict, tensors, return_tensors: bool):
+    """The closing of both: ``out`` handed over into the caller's ``stats``, the answer as it is or as NumPy arrays."""
+    if stats is not None:
+        stats.clear()
+        stats.update(out)
+    return tensors if return_tensors else tuple(t.cpu().numpy() for t in tensors)
 
 
 def exact_top_k(queries, corpus, k: int, *, row_ids=None, method: str = "auto", return_tensors: bool = False,
@@ -184,27 +219,12 @@ def exact_top_k(queries, corpus, k: int, *, row_ids=None, method: str = "auto", 
         raise ValueError("k must be > 0")
     k = int(k)
     torch = _native.require_gpu()
-    lib = _native.load()
-    corpus_entry(corpus, "ragged")
+    d_q, d_ids, q, m, dim = _search_args(queries, corpus, row_ids, "exact_top_k")
     dev = corpus.device
     with torch.cuda.device(dev):
-        d_q = _on_device(torch, queries, np.float32)
-        if d_q.dim() != 2 or int(d_q.shape[1]) != int(corpus.shape[1]):
-            raise ValueError(f"queries must have shape (q, {int(corpus.shape[1])}); received {tuple(d_q.shape)}")
-        d_q = d_q.to(device=dev, dtype=torch.float32).contiguous()
-        q, m, dim = int(d_q.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
-        if dim > _SCAN_MAX_DIM or m > _SCAN_MAX_ROWS:
-            # (beyond the scan and beyond the rerank's entries alike: what a rerank of such rows raises, before any launch)
-            raise _native.NativeLibraryError(f"exact_top_k: shape outside kernel limits (LSHRS_E_TOOLARGE): {m} rows of {dim} "
-                                             f"elements; at most {_SCAN_MAX_ROWS} rows of {_SCAN_MAX_DIM}")
-        d_ids = None
-        if row_ids is not None:
-            d_ids = _on_device(torch, row_ids, np.int64).to(device=dev, dtype=torch.int64).contiguous()
-            if d_ids.dim() != 1 or int(d_ids.shape[0]) != m:
-                raise ValueError(f"row_ids must have shape ({m},); received {tuple(d_ids.shape)}")
         live = m if d_ids is None else int((d_ids >= 0).sum())
         kk = min(k, live)
-        max_window = int(lib.lshrs_scan_max_window())
+        max_window = scan_max_window()
         use_scan = method == "scan" or (method == "auto" and 2 * k <= max_window)
         window = choose_window(k, max_window)
         eps = scan_epsilon(corpus.dtype, dim)
@@ -219,7 +239,7 @@ def exact_top_k(queries, corpus, k: int, *, row_ids=None, method: str = "auto", 
             key = torch.where(rows >= 0, wid, torch.full_like(wid, torch.iinfo(torch.int64).max))
             by_id = torch.argsort(key, dim=1)
             rows_s, wid = torch.gather(rows, 1, by_id).contiguous(), torch.gather(wid, 1, by_id)
-            exact, err2 = _rescore(torch, lib, corpus, d_q, rows_s, count)
+            exact, err2 = _rescore(torch, corpus, d_q, rows_s, count)
             if int(err.item()) & 5 or int(err2.item()) & 5:
                 raise ValueError("Cannot normalize zero vector")
             kw = min(kk, window)
@@ -247,12 +267,7 @@ def exact_top_k(queries, corpus, k: int, *, row_ids=None, method: str = "auto", 
             else:
                 ids[todo], scores[todo] = g_ids, g_scores
             out["gathered"] = int(sub.shape[0])
-    if stats is not None:
-        stats.clear()
-        stats.update(out)
-    if return_tensors:
-        return ids, scores
-    return ids.cpu().numpy(), scores.cpu().numpy()
+    return _finish(stats, out, (ids, scores), return_tensors)
 
 
 # ------------------------------------------------------------------------------------------
@@ -297,7 +312,7 @@ def scan_above(corpus, queries, bars, capacity: int, row_ids=None):
     capacity)`` slots are pairs, in no particular order; ``total`` counts every pair that reached its bar."""
     torch = _native.require_gpu()
     lib = _native.load()
-    entry = corpus_entry(corpus, "ragged").replace("lshrs_cosine_ragged_", "lshrs_scan_above_")
+    entry = "lshrs_scan_above_" + corpus_suffix(corpus)
     dev = corpus.device
     q, m, dim = int(queries.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
     capacity = int(capacity)
@@ -308,11 +323,8 @@ def scan_above(corpus, queries, bars, capacity: int, row_ids=None):
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     if q == 0:
         return out_q, out_row, out_approx, total, err
-    nbytes = int(lib.lshrs_scan_above_workspace_bytes(q, m, dim))
-    if nbytes < 0:
-        _native.check(nbytes, "lshrs_scan_above_workspace_bytes")
     with torch.cuda.device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _scan_workspace(torch, lib, "lshrs_scan_above_workspace_bytes", dev, q, m, dim)
         _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim,
                                           row_ids.data_ptr() if row_ids is not None else None, queries.data_ptr(), q,
                                           bars.data_ptr(), capacity, out_q.data_ptr() if capacity else None,
@@ -350,23 +362,9 @@ def exact_above(queries, corpus, threshold, *, row_ids=None, max_pairs: int = 1 
     max_pairs = int(max_pairs)
     thr64 = _check_above_args(shape[0], threshold, max_pairs)
     torch = _native.require_gpu()
-    lib = _native.load()
-    corpus_entry(corpus, "ragged")
+    d_q, d_ids, q, m, dim = _search_args(queries, corpus, row_ids, "exact_above")
     dev = corpus.device
     with torch.cuda.device(dev):
-        d_q = _on_device(torch, queries, np.float32)
-        if d_q.dim() != 2 or int(d_q.shape[1]) != int(corpus.shape[1]):
-            raise ValueError(f"queries must have shape (q, {int(corpus.shape[1])}); received {tuple(d_q.shape)}")
-        d_q = d_q.to(device=dev, dtype=torch.float32).contiguous()
-        q, m, dim = int(d_q.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
-        if dim > _SCAN_MAX_DIM or m > _SCAN_MAX_ROWS:
-            raise _native.NativeLibraryError(f"exact_above: shape outside kernel limits (LSHRS_E_TOOLARGE): {m} rows of {dim} "
-                                             f"elements; at most {_SCAN_MAX_ROWS} rows of {_SCAN_MAX_DIM}")
-        d_ids = None
-        if row_ids is not None:
-            d_ids = _on_device(torch, row_ids, np.int64).to(device=dev, dtype=torch.int64).contiguous()
-            if d_ids.dim() != 1 or int(d_ids.shape[0]) != m:
-                raise ValueError(f"row_ids must have shape ({m},); received {tuple(d_ids.shape)}")
         eps = scan_epsilon(corpus.dtype, dim)
         out = {"queries": q, "emitted": 0, "kept": 0, "launches": 0, "epsilon": eps}
         ids = torch.empty((0,), dtype=torch.int64, device=dev)
@@ -396,13 +394,7 @@ def exact_above(queries, corpus, threshold, *, row_ids=None, max_pairs: int = 1 
                 prow = prow[:emitted][by_q].contiguous()
                 count = torch.bincount(pq, minlength=q)
                 off = (torch.cumsum(count, 0) - count).contiguous()
-                exact = torch.empty((emitted,), dtype=torch.float32, device=dev)
-                err2 = torch.zeros(1, dtype=torch.int32, device=dev)
-                entry = corpus_entry(corpus, "ragged")
-                cnt32 = count.to(torch.int32)
-                _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim, d_q.data_ptr(), q,
-                                                  prow.data_ptr(), off.data_ptr(), cnt32.data_ptr(), emitted, exact.data_ptr(),
-                                                  err2.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), entry)
+                exact, err2 = cosine_ragged_device(corpus, d_q, prow, off, count.to(torch.int32), emitted)
                 if int(err2.item()) & 5:
                     raise ValueError("Cannot normalize zero vector")
                 keep = exact >= t32[pq]                 # (a NaN is not kept)
@@ -419,12 +411,7 @@ def exact_above(queries, corpus, threshold, *, row_ids=None, max_pairs: int = 1 
                 ids, scores = pid.contiguous(), exact.contiguous()
                 bounds[1:] = torch.cumsum(torch.bincount(pq, minlength=q), 0)
                 out["kept"] = int(ids.shape[0])
-    if stats is not None:
-        stats.clear()
-        stats.update(out)
-    if return_tensors:
-        return ids, scores, bounds
-    return ids.cpu().numpy(), scores.cpu().numpy(), bounds.cpu().numpy()
+    return _finish(stats, out, (ids, scores, bounds), return_tensors)
 
 
 def above_recall(truth_ids, truth_scores, truth_bounds, cand_ids, cand_bounds, num_bands: int, rows_per_band: int) -> Dict:

@@ -53,7 +53,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
     _hostblas.build(force=force, verbose=verbose)
     with _lock:
-        header = max(os.path.getmtime(os.path.join(INCLUDE, "lshrs_hip.h")), os.path.getmtime(os.path.join(CSRC, "lshrs_common.h")))
+        header = max(os.path.getmtime(p) for p in (os.path.join(INCLUDE, "lshrs_hip.h"), os.path.join(CSRC, "lshrs_common.h"),
+                                                   os.path.join(CSRC, "scan_pass.inc")))
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         objdir = os.path.join(CSRC, "_obj")
         os.makedirs(objdir, exist_ok=True)

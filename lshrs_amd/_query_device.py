@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _native
 from .similarity import _upload as upload
-from .similarity import corpus_entry
+from .similarity import corpus_entry, corpus_suffix, cosine_ragged_device
 from .vectors import NO_VECTOR_MSG
 from .windows import _U
 
@@ -263,20 +263,16 @@ def rank_and_cut(lists: _Lists, top_k: Optional[int], top_p: Optional[float], *,
                            top_p=-1.0 if top_p is None else float(top_p), keep_out=keep)
         scores = err = None
         if top_p is not None and lists.total:
-            entry = corpus_entry(corpus, "ragged")
+            corpus_suffix(corpus)                     # (before anything is enqueued)
             rows = lists.cand_ids if cand_rows is None else cand_rows
-            scores = torch.empty(max(1, lists.total), dtype=torch.float32, device=dev)
-            err = torch.zeros(1, dtype=torch.int32, device=dev)
+            err = torch.zeros(1, dtype=torch.int32, device=dev)      # (one word for both kernels' reports)
             if idmap is not None and cand_rows is None:
                 rows = torch.empty_like(lists.cand_ids)
                 _native.check(lib.lshrs_idmap_lookup_ragged_i64(idmap[0].data_ptr(), int(idmap[1]), lists.cand_ids.data_ptr(),
                                                                 lists.pair_off.data_ptr(), lists.ucount.data_ptr(), nq,
                                                                 lists.total, rows.data_ptr(), err.data_ptr(), stream),
                               "lshrs_idmap_lookup_ragged_i64")
-            _native.check(getattr(lib, entry)(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)),
-                                              int(corpus.shape[1]), queries_dev.data_ptr(), nq, rows.data_ptr(),
-                                              lists.pair_off.data_ptr(), lists.ucount.data_ptr(), lists.total,
-                                              scores.data_ptr(), err.data_ptr(), stream), entry)
+            scores, err = cosine_ragged_device(corpus, queries_dev, rows, lists.pair_off, lists.ucount, lists.total, err=err)
         bounds = out_off.cpu().numpy()                # (waits for the scan - and whatever is in front of it - only: the rerank runs on)
         kept = int(bounds[-1])
         # ids and scores side by side in ONE block: one copy back

@@ -604,6 +604,37 @@ class LSHRS:
                 return qh.split_rows(ids.tolist(), keep)
             return qh.split_rows(list(zip(ids.tolist(), scores.astype(np.float64).tolist())), keep)
 
+    def _search_queries(self, vectors):
+        """The queries of an exact search as what it searches with: a float32 device tensor where ``vectors`` lives on a
+        GPU, else a float32 host array; ``(n, dim)`` or the ``ValueError`` every query raises."""
+        resident = _device_tensor(vectors)
+        arr = resident if resident is not None else np.asarray(vectors, dtype=np.float32)
+        if len(arr.shape) != 2 or int(arr.shape[1]) != self._dim:
+            raise ValueError(f"Vectors must have shape (n, {self._dim}); received {tuple(arr.shape)}")
+        return arr if resident is None else resident.float()
+
+    def _search_corpus(self, caller: str, in_store, in_tensor, arr, what):
+        """One exact search of ``arr`` for ``what`` (a ``top_k`` / a threshold): ``in_store`` (``DeviceVectors.search`` /
+        ``search_above``) where the index reranks from a ``DeviceVectors``, else ``in_tensor`` (``exact_top_k`` /
+        ``exact_above``) over the attached corpus on its device.  Sets ``last_search_stats``; without a corpus or a store,
+        raises in the name of ``caller``."""
+        corpus = self._rerank_corpus()
+        if corpus is None:
+            self._require_vector_fetch_fn()
+            raise RuntimeError(f"{caller} needs the indexed vectors on the device: set_corpus(...) or keep_vectors=...")
+        if isinstance(corpus, DeviceVectors):
+            got = in_store(corpus, arr, what)
+            self.last_search_stats = dict(corpus.last_search_stats)
+            return got
+        from . import _query_device as qd
+
+        stats: Dict[str, Any] = {}
+        table = qd.corpus_on(corpus, getattr(corpus, "device", None) if _device_tensor(corpus) is not None
+                             else self._hasher._torch_device(), self._dim)
+        got = in_tensor(arr, table, what, stats=stats)
+        self.last_search_stats = stats
+        return got
+
     def search_exact(self, vectors, top_k: int = 10, *, return_arrays: bool = False):
         """The ``top_k`` indexed vectors nearest to every query by cosine, EXACTLY: every vector of the attached corpus
         (:meth:`set_corpus`), else of the index's own store (``keep_vectors``), is scored - no buckets involved
@@ -614,31 +645,13 @@ class LSHRS:
         there)``.  Without a corpus or a store it raises what a rerank without a fetch function raises.  ``last_search_stats``
         tells what the call did.  A corpus that :meth:`set_corpus` was given as a HOST array is uploaded by every call, as every
         reranked query uploads it (and twice by :meth:`recall`, once for each of its halves): attach a device tensor."""
-        resident = _device_tensor(vectors)
-        arr = resident if resident is not None else np.asarray(vectors, dtype=np.float32)
-        if len(arr.shape) != 2 or int(arr.shape[1]) != self._dim:
-            raise ValueError(f"Vectors must have shape (n, {self._dim}); received {tuple(arr.shape)}")
-        if resident is not None:
-            arr = resident.float()
+        from ._exact import exact_top_k
+
+        arr = self._search_queries(vectors)
         qh.check_cut(top_k, None)
         if top_k is None:
             raise ValueError("search_exact needs a top_k")
-        corpus = self._rerank_corpus()
-        if corpus is None:
-            self._require_vector_fetch_fn()
-            raise RuntimeError("search_exact needs the indexed vectors on the device: set_corpus(...) or keep_vectors=...")
-        if isinstance(corpus, DeviceVectors):
-            ids, scores = corpus.search(arr, top_k)
-            self.last_search_stats = dict(corpus.last_search_stats)
-        else:
-            from . import _query_device as qd
-            from ._exact import exact_top_k
-
-            stats: Dict[str, Any] = {}
-            table = qd.corpus_on(corpus, getattr(corpus, "device", None) if _device_tensor(corpus) is not None
-                                 else self._hasher._torch_device(), self._dim)
-            ids, scores = exact_top_k(arr, table, top_k, stats=stats)
-            self.last_search_stats = stats
+        ids, scores = self._search_corpus("search_exact", DeviceVectors.search, exact_top_k, arr, top_k)
         if return_arrays:
             return ids, scores
         with _gc_paused():
@@ -665,28 +678,10 @@ class LSHRS:
         errors where there is none.  Returns per query ``[(id, score), ...]``, scores descending and equal scores by ascending
         id - or ``(ids, scores, bounds)`` as :meth:`query_many` returns them with ``return_arrays``.  ``last_search_stats``
         tells what the call did."""
-        resident = _device_tensor(vectors)
-        arr = resident if resident is not None else np.asarray(vectors, dtype=np.float32)
-        if len(arr.shape) != 2 or int(arr.shape[1]) != self._dim:
-            raise ValueError(f"Vectors must have shape (n, {self._dim}); received {tuple(arr.shape)}")
-        if resident is not None:
-            arr = resident.float()
-        corpus = self._rerank_corpus()
-        if corpus is None:
-            self._require_vector_fetch_fn()
-            raise RuntimeError("search_exact_above needs the indexed vectors on the device: set_corpus(...) or keep_vectors=...")
-        if isinstance(corpus, DeviceVectors):
-            ids, scores, bounds = corpus.search_above(arr, threshold)
-            self.last_search_stats = dict(corpus.last_search_stats)
-        else:
-            from . import _query_device as qd
-            from ._exact import exact_above
+        from ._exact import exact_above
 
-            stats: Dict[str, Any] = {}
-            table = qd.corpus_on(corpus, getattr(corpus, "device", None) if _device_tensor(corpus) is not None
-                                 else self._hasher._torch_device(), self._dim)
-            ids, scores, bounds = exact_above(arr, table, threshold, stats=stats)
-            self.last_search_stats = stats
+        arr = self._search_queries(vectors)
+        ids, scores, bounds = self._search_corpus("search_exact_above", DeviceVectors.search_above, exact_above, arr, threshold)
         if return_arrays:
             return ids, scores, bounds
         with _gc_paused():

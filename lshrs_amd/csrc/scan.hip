@@ -20,6 +20,7 @@
 // scan_merge_kernel orders the slices' winners of a query in LDS.  No global atomics but the error bits.
 // Range scan (scan_above_kernel, lshrs_scan_above_*): the same first pass with no selection at all - every (query, live row)
 // whose approximate score reaches the query's bar is emitted to flat arrays through one global cursor (lshrs_amd.exact_above).
+// The pass (rows in, dot products and norms out) is written once, in scan_pass.inc, and compiled into both kernels.
 // ABI and reference citations: include/lshrs_hip.h.  Design notes, the epsilon derivation and the roof: DESIGN.md.
 #include "lshrs_common.h"
 
@@ -312,73 +313,11 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
   __syncthreads();
 
   for (int64_t base = row_begin; base < row_end; base += kScanPassRows) {
-    const T* rowp[2];
     bool live[2];
     int64_t row0[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      row0[t] = base + wave * 64 + t * 32;
-      const int64_t row = row0[t] + r;
-      const bool valid = row < row_end;
-      live[t] = valid && (row_ids == nullptr || row_ids[row] >= 0);
-      rowp[t] = corpus + (valid ? row : row_begin) * ldc;      // (a row past the end reads the slice's first row, unused)
-    }
     f32x16 acc[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][cb][i] = 0.f;
-    float nn[2] = {0.f, 0.f};
-
-    // chunk c + 1's rows and B fragments are asked for before chunk c is multiplied, so that the loads fly under the MFMAs
-    auto load_chunk = [&](int c, ScanRaw<E> (&raw)[2], u32x4 (&bst)[4]) {
-      const int k0 = c * kScanKChunk + 32 * h;
-      if (ALIGNED && (c + 1) * kScanKChunk <= dim) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) raw[t] = scan_load_vec<E>(rowp[t] + k0);
-      } else {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) raw[t] = scan_load_elems<E>(rowp[t], k0, dim);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) bst[i] = bimg[(int64_t)c * (kScanChunkBytes / 16) + i * kScanThreads + tid];
-    };
-    // (one-term rows only: a two-term row's fragments leave no registers for a second chunk)
-    constexpr bool kAhead = !kTwo;
-    ScanRaw<E> nraw[2];
-    u32x4 nbst[4];
-    if constexpr (kAhead) load_chunk(0, nraw, nbst);
-    for (int c = 0; c < nchunks; ++c) {
-      if constexpr (!kAhead) load_chunk(c, nraw, nbst);
-      ScanRaw<E> raw[2] = {nraw[0], nraw[1]};
-      __syncthreads();                    // the last chunk's fragments have been read
-#pragma unroll
-      for (int i = 0; i < 4; ++i) bl[i * kScanThreads + tid] = nbst[i];
-      __syncthreads();
-      if constexpr (kAhead)
-        if (c + 1 < nchunks) load_chunk(c + 1, nraw, nbst);
-
-      u32x4 ahi[2][4], amid[2][4];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) scan_fragments<E>(raw[t], ahi[t], amid[t], nn[t]);
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          const bf16x8 bh = __builtin_bit_cast(bf16x8, bl[((0 * 4 + s) * 2 + cb) * 64 + lane]);
-          const bf16x8 bm = __builtin_bit_cast(bf16x8, bl[((1 * 4 + s) * 2 + cb) * 64 + lane]);
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            const bf16x8 ah = __builtin_bit_cast(bf16x8, ahi[t][s]);
-            acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t][cb], 0, 0, 0);
-            acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[t][cb], 0, 0, 0);
-            if constexpr (kTwo)
-              acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, amid[t][s]), bh, acc[t][cb], 0, 0, 0);
-          }
-        }
-    }
+    float nn[2];
+#include "scan_pass.inc"
 
     // the finished 256 x 64 tile: acc[t][cb][i] is row (i & 3) + 8 (i >> 2) + 4 h of tile t, query cb * 32 + r
 #pragma unroll
@@ -444,11 +383,10 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
 }
 
 // ------------------------------------------------------------------------------------------
-// one pass of a workgroup: 256 rows from `base` (64 per wave, two 32-row tiles) against the query tile's image, all chunks of k.
-// Leaves acc[t][cb] (the dot products of tile t with column block cb), nn[t] (this lane's half of ||row||^2), live[t] and
-// row0[t] (the tile's first row).  Every thread of the workgroup calls it (it synchronises on the B chunk in LDS, `bl`).
-// A copy of scan_kernel's main loop, statement for statement: calling this from scan_kernel moved its register allocation
-// (spills and scratch of seven of its ten instantiations), so that kernel keeps its loop inline and the two are kept alike by hand.
+// one pass of a workgroup as a function, for scan_above_kernel: the text of scan_pass.inc (which says what it takes and leaves).
+// scan_kernel includes the same text inline instead of calling this: the call moved its register allocation (spills and
+// scratch of seven of its ten instantiations - measured in commit f6cea70, "Exact range search: every stored vector at or above a
+// cosine threshold"), while the included text compiles to the code the kernel had with the loop written out in it.
 // ------------------------------------------------------------------------------------------
 template <typename E, bool ALIGNED>
 __device__ __forceinline__ void scan_pass(const typename ScanElem<E>::T* __restrict__ corpus, int64_t ldc, int dim, int nchunks,
@@ -459,70 +397,7 @@ __device__ __forceinline__ void scan_pass(const typename ScanElem<E>::T* __restr
   constexpr bool kTwo = ScanElem<E>::kTerms == 2;
   const int lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
-  const T* rowp[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    row0[t] = base + wave * 64 + t * 32;
-    const int64_t row = row0[t] + r;
-    const bool valid = row < row_end;
-    live[t] = valid && (row_ids == nullptr || row_ids[row] >= 0);
-    rowp[t] = corpus + (valid ? row : row_begin) * ldc;      // (a row past the end reads the slice's first row, unused)
-  }
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[t][cb][i] = 0.f;
-  nn[0] = nn[1] = 0.f;
-
-  // chunk c + 1's rows and B fragments are asked for before chunk c is multiplied, so that the loads fly under the MFMAs
-  auto load_chunk = [&](int c, ScanRaw<E> (&raw)[2], u32x4 (&bst)[4]) {
-    const int k0 = c * kScanKChunk + 32 * h;
-    if (ALIGNED && (c + 1) * kScanKChunk <= dim) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) raw[t] = scan_load_vec<E>(rowp[t] + k0);
-    } else {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) raw[t] = scan_load_elems<E>(rowp[t], k0, dim);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) bst[i] = bimg[(int64_t)c * (kScanChunkBytes / 16) + i * kScanThreads + tid];
-  };
-  // (one-term rows only: a two-term row's fragments leave no registers for a second chunk)
-  constexpr bool kAhead = !kTwo;
-  ScanRaw<E> nraw[2];
-  u32x4 nbst[4];
-  if constexpr (kAhead) load_chunk(0, nraw, nbst);
-  for (int c = 0; c < nchunks; ++c) {
-    if constexpr (!kAhead) load_chunk(c, nraw, nbst);
-    ScanRaw<E> raw[2] = {nraw[0], nraw[1]};
-    __syncthreads();                    // the last chunk's fragments have been read
-#pragma unroll
-    for (int i = 0; i < 4; ++i) bl[i * kScanThreads + tid] = nbst[i];
-    __syncthreads();
-    if constexpr (kAhead)
-      if (c + 1 < nchunks) load_chunk(c + 1, nraw, nbst);
-
-    u32x4 ahi[2][4], amid[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) scan_fragments<E>(raw[t], ahi[t], amid[t], nn[t]);
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const bf16x8 bh = __builtin_bit_cast(bf16x8, bl[((0 * 4 + s) * 2 + cb) * 64 + lane]);
-        const bf16x8 bm = __builtin_bit_cast(bf16x8, bl[((1 * 4 + s) * 2 + cb) * 64 + lane]);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const bf16x8 ah = __builtin_bit_cast(bf16x8, ahi[t][s]);
-          acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t][cb], 0, 0, 0);
-          acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[t][cb], 0, 0, 0);
-          if constexpr (kTwo)
-            acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, amid[t][s]), bh, acc[t][cb], 0, 0, 0);
-        }
-      }
-  }
+#include "scan_pass.inc"
 }
 
 // ------------------------------------------------------------------------------------------
@@ -678,20 +553,62 @@ inline void scan_slices(int64_t m, int qtiles, int64_t lds, int64_t limit, int64
   slices = (int)((m + rps - 1) / rps);
 }
 
-inline int scan_plan(int32_t q, int64_t m, int32_t dim, int32_t window, ScanPlan& p) {
-  if (q < 0 || m <= 0 || dim <= 0 || window <= 0 || window > kScanMaxWindow) return LSHRS_E_BADARG;
+// what the two plans share: the ranges of q, m and dim, and what follows from q and dim alone
+inline int scan_geometry(int32_t q, int64_t m, int32_t dim, ScanPlan& p) {
+  if (q < 0 || m <= 0 || dim <= 0) return LSHRS_E_BADARG;
   if (dim > kScanMaxDim || m > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
   p.qtiles = (q + kScanQTile - 1) / kScanQTile;
   if (p.qtiles > 65535) return LSHRS_E_TOOLARGE;
   p.nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
+  p.image_bytes = (int64_t)p.qtiles * p.nchunks * kScanChunkBytes;
+  p.qnorm_bytes = (int64_t)p.qtiles * kScanQTile * (int64_t)sizeof(float);
+  return 0;
+}
+
+inline int scan_plan(int32_t q, int64_t m, int32_t dim, int32_t window, ScanPlan& p) {
+  if (window <= 0 || window > kScanMaxWindow) return LSHRS_E_BADARG;
+  const int bad = scan_geometry(q, m, dim, p);
+  if (bad) return bad;
   p.cap = 64;
   while (p.cap < 2 * window) p.cap <<= 1;
   const int64_t lds = (int64_t)kScanChunkBytes + (int64_t)kScanQTile * p.cap * 8 + kScanQTile * 12;
   scan_slices(m, p.qtiles, lds, kScanMergeItems / window, p.rows_per_slice, p.slices);
-  p.image_bytes = (int64_t)p.qtiles * p.nchunks * kScanChunkBytes;
-  p.qnorm_bytes = (int64_t)p.qtiles * kScanQTile * (int64_t)sizeof(float);
   p.parts_bytes = (int64_t)q * p.slices * window * (int64_t)sizeof(uint64_t);
   return 0;
+}
+
+// range scan: no merge limit, residency from scan_above_kernel's own LDS (the B chunk)
+inline int scan_above_plan(int32_t q, int64_t m, int32_t dim, ScanPlan& p) {
+  const int bad = scan_geometry(q, m, dim, p);
+  if (bad) return bad;
+  p.cap = 0;
+  scan_slices(m, p.qtiles, kScanChunkBytes, INT64_MAX, p.rows_per_slice, p.slices);
+  p.parts_bytes = 0;
+  return 0;
+}
+
+// the front of both entries: the image and the query norms at the head of the workspace, written by scan_prep_kernel and
+// scan_qnorm_kernel, and whether the corpus takes the ALIGNED instantiation (16-byte vector loads of whole chunks)
+struct ScanFront {
+  u32x4* image;
+  float* qnorm;
+  bool aligned;
+};
+
+template <typename E>
+ScanFront scan_front(const ScanPlan& p, const typename ScanElem<E>::T* corpus, int64_t ldc, int32_t dim, const float* queries,
+                     int32_t q, void* workspace, int32_t* err, hipStream_t s) {
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  ScanFront f;
+  f.image = reinterpret_cast<u32x4*>(ws);
+  f.qnorm = reinterpret_cast<float*>(ws + p.image_bytes);
+  f.aligned = (ldc % ScanElem<E>::kAlign == 0) && ((reinterpret_cast<uintptr_t>(corpus) & 15) == 0);
+  const int qpad = p.qtiles * kScanQTile;
+  hipLaunchKernelGGL(scan_prep_kernel, dim3((unsigned)p.nchunks, (unsigned)p.qtiles), dim3(kScanThreads), 0, s, queries, q, dim,
+                     p.nchunks, f.image);
+  hipLaunchKernelGGL(scan_qnorm_kernel, dim3((unsigned)(qpad / kScanWaves)), dim3(kScanThreads), 0, s, queries, q, qpad, dim,
+                     f.qnorm, err);
+  return f;
 }
 
 template <typename E, bool ALIGNED>
@@ -721,19 +638,10 @@ int scan_topk(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int
       workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 15) || ldc < dim)
     return LSHRS_E_BADARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  u32x4* image = reinterpret_cast<u32x4*>(ws);
-  float* qnorm = reinterpret_cast<float*>(ws + p.image_bytes);
-  uint64_t* parts = reinterpret_cast<uint64_t*>(ws + p.image_bytes + p.qnorm_bytes);
-  const int qpad = p.qtiles * kScanQTile;
-  hipLaunchKernelGGL(scan_prep_kernel, dim3((unsigned)p.nchunks, (unsigned)p.qtiles), dim3(kScanThreads), 0, s, queries, q, dim,
-                     p.nchunks, image);
-  hipLaunchKernelGGL(scan_qnorm_kernel, dim3((unsigned)(qpad / kScanWaves)), dim3(kScanThreads), 0, s, queries, q, qpad, dim,
-                     qnorm, err);
-  constexpr int kAlign = ScanElem<E>::kAlign;
-  const bool aligned = (ldc % kAlign == 0) && ((reinterpret_cast<uintptr_t>(corpus) & 15) == 0);
-  const int rc = aligned ? scan_launch<E, true>(p, corpus, m, ldc, dim, row_ids, image, qnorm, q, window, parts, err, s)
-                         : scan_launch<E, false>(p, corpus, m, ldc, dim, row_ids, image, qnorm, q, window, parts, err, s);
+  uint64_t* parts = reinterpret_cast<uint64_t*>(static_cast<unsigned char*>(workspace) + p.image_bytes + p.qnorm_bytes);
+  const ScanFront f = scan_front<E>(p, corpus, ldc, dim, queries, q, workspace, err, s);
+  const int rc = f.aligned ? scan_launch<E, true>(p, corpus, m, ldc, dim, row_ids, f.image, f.qnorm, q, window, parts, err, s)
+                           : scan_launch<E, false>(p, corpus, m, ldc, dim, row_ids, f.image, f.qnorm, q, window, parts, err, s);
   if (rc) return rc;
   const int n = p.slices * window;
   int npad = 2;
@@ -747,21 +655,6 @@ int scan_topk(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int
   hipLaunchKernelGGL(scan_merge_kernel, dim3((unsigned)q), dim3(kScanThreads), merge_lds, s, parts, n, npad, window, out_rows,
                      out_approx, out_count);
   return -(int)hipGetLastError();
-}
-
-// ---- range scan: geometry without the merge limit, residency from scan_above_kernel's own LDS (the B chunk) ----
-inline int scan_above_plan(int32_t q, int64_t m, int32_t dim, ScanPlan& p) {
-  if (q < 0 || m <= 0 || dim <= 0) return LSHRS_E_BADARG;
-  if (dim > kScanMaxDim || m > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
-  p.qtiles = (q + kScanQTile - 1) / kScanQTile;
-  if (p.qtiles > 65535) return LSHRS_E_TOOLARGE;
-  p.nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
-  p.cap = 0;
-  scan_slices(m, p.qtiles, kScanChunkBytes, INT64_MAX, p.rows_per_slice, p.slices);
-  p.image_bytes = (int64_t)p.qtiles * p.nchunks * kScanChunkBytes;
-  p.qnorm_bytes = (int64_t)p.qtiles * kScanQTile * (int64_t)sizeof(float);
-  p.parts_bytes = 0;
-  return 0;
 }
 
 template <typename E>
@@ -779,26 +672,17 @@ int scan_above(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, in
       (addr(queries) & 3) || ldc < dim)
     return LSHRS_E_BADARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  u32x4* image = reinterpret_cast<u32x4*>(ws);
-  float* qnorm = reinterpret_cast<float*>(ws + p.image_bytes);
-  const int qpad = p.qtiles * kScanQTile;
   const hipError_t e = hipMemsetAsync(total, 0, sizeof(uint64_t), s);
   if (e != hipSuccess) return -(int)e;
-  hipLaunchKernelGGL(scan_prep_kernel, dim3((unsigned)p.nchunks, (unsigned)p.qtiles), dim3(kScanThreads), 0, s, queries, q, dim,
-                     p.nchunks, image);
-  hipLaunchKernelGGL(scan_qnorm_kernel, dim3((unsigned)(qpad / kScanWaves)), dim3(kScanThreads), 0, s, queries, q, qpad, dim,
-                     qnorm, err);
-  constexpr int kAlign = ScanElem<E>::kAlign;
-  const bool aligned = (ldc % kAlign == 0) && ((addr(corpus) & 15) == 0);
+  const ScanFront f = scan_front<E>(p, corpus, ldc, dim, queries, q, workspace, err, s);
   const dim3 grid((unsigned)p.slices, (unsigned)p.qtiles), block(kScanThreads);
   unsigned long long* cursor = reinterpret_cast<unsigned long long*>(total);
-  if (aligned)
-    hipLaunchKernelGGL((scan_above_kernel<E, true>), grid, block, (size_t)kScanChunkBytes, s, corpus, m, ldc, dim, row_ids, image,
-                       qnorm, bars, q, p.rows_per_slice, capacity, out_query, out_row, out_approx, cursor, err);
+  if (f.aligned)
+    hipLaunchKernelGGL((scan_above_kernel<E, true>), grid, block, (size_t)kScanChunkBytes, s, corpus, m, ldc, dim, row_ids,
+                       f.image, f.qnorm, bars, q, p.rows_per_slice, capacity, out_query, out_row, out_approx, cursor, err);
   else
-    hipLaunchKernelGGL((scan_above_kernel<E, false>), grid, block, (size_t)kScanChunkBytes, s, corpus, m, ldc, dim, row_ids, image,
-                       qnorm, bars, q, p.rows_per_slice, capacity, out_query, out_row, out_approx, cursor, err);
+    hipLaunchKernelGGL((scan_above_kernel<E, false>), grid, block, (size_t)kScanChunkBytes, s, corpus, m, ldc, dim, row_ids,
+                       f.image, f.qnorm, bars, q, p.rows_per_slice, capacity, out_query, out_row, out_approx, cursor, err);
   return -(int)hipGetLastError();
 }
 }  // namespace

@@ -26,6 +26,7 @@ import numpy as np
 from . import _native
 
 __all__ = ["l2_norm", "cosine_similarity", "top_k_cosine", "rerank_batch", "rerank_padded", "cosine_scores_device",
+           "cosine_ragged_device",
            "l2_normalize_device", "quantize_rows",
            "topk_desc_device"]
 
@@ -55,10 +56,10 @@ _CORPUS_ENTRY = {"float32": "f32", "bfloat16": "bf16", "float16": "f16"}
 _CORPUS_ENTRY_8BIT = {"int8": "i8", "float8_e4m3fn": "f8e4m3"}
 
 
-def corpus_entry(corpus, form: str, dim: Optional[int] = None) -> str:
-    """The one place that decides which corpora the rerank reads on the device: a CUDA tensor of float32, bfloat16, float16,
-    int8 or float8_e4m3fn, shape ``(m, dim)`` with a unit inner stride (any row stride).  Returns the name of the C entry of
-    ``form`` ("batch" or "ragged") that scores against it; raises :class:`CorpusError` naming what is accepted otherwise."""
+def corpus_suffix(corpus, dim: Optional[int] = None) -> str:
+    """The one place that decides which corpora the kernels read on the device: a CUDA tensor of float32, bfloat16, float16,
+    int8 or float8_e4m3fn, shape ``(m, dim)`` with a unit inner stride (any row stride).  Returns the suffix of the C entries
+    that read it ("f32", "bf16", "f16", "i8" or "f8e4m3"); raises :class:`CorpusError` naming what is accepted otherwise."""
     torch = _native.require_gpu()
     suffix = None
     if isinstance(corpus, torch.Tensor):
@@ -70,7 +71,13 @@ def corpus_entry(corpus, form: str, dim: Optional[int] = None) -> str:
         raise CorpusError(f"corpus must be a float32, bfloat16 or float16 (or int8 or float8_e4m3fn) device tensor of shape "
                           f"{want} with unit inner stride; got {getattr(corpus, 'dtype', type(corpus).__name__)} "
                           f"{tuple(getattr(corpus, 'shape', ()))}")
-    return f"lshrs_cosine_{form}_{suffix}"
+    return suffix
+
+
+def corpus_entry(corpus, form: str, dim: Optional[int] = None) -> str:
+    """The name of the rerank's C entry of ``form`` ("batch" or "ragged") that scores against ``corpus``
+    (:func:`corpus_suffix`: what is accepted, and the :class:`CorpusError` otherwise)."""
+    return f"lshrs_cosine_{form}_{corpus_suffix(corpus, dim)}"
 
 
 def quantize_rows(x, dtype):
@@ -155,6 +162,31 @@ def cosine_scores_device(corpus, queries, cand_idx=None, *, c: Optional[int] = N
                                 c, scores.data_ptr(), status.data_ptr(), qstatus.data_ptr(), stream),
             entry)
     return scores, status, qstatus
+
+
+def cosine_ragged_device(corpus, queries, rows, offsets, counts, total: int, *, scores=None, err=None):
+    """Device-level entry of the ragged form (``lshrs_cosine_ragged_*``): tensors in, tensors out, all on the corpus's device.
+
+    corpus (m, dim) as :func:`corpus_suffix` accepts it, queries (q, dim) f32; query i's candidates are the corpus
+    rows ``rows[offsets[i] : offsets[i] + counts[i]]`` (rows, offsets int64; counts int32) and their scores land at the same
+    places of ``scores``; ``total``: the length of ``rows`` the lists lie within.  ``scores`` (float32, at least ``total``)
+    and ``err`` (int32[1], to which the kernel ORs its error bits: include/lshrs_hip.h) are allocated here - ``(max(1,
+    total),)``, and zeroed - unless given.  Launches on the current stream of the corpus's device; returns ``(scores, err)``."""
+    torch = _native.require_gpu()
+    lib = _native.load()
+    entry = corpus_entry(corpus, "ragged")
+    dev = corpus.device
+    queries = queries.contiguous()          # (the entry takes no row stride for them; a no-op for what the callers hand in)
+    if scores is None:
+        scores = torch.empty((max(1, int(total)),), dtype=torch.float32, device=dev)
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(getattr(lib, entry)(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)), int(corpus.shape[1]),
+                                          queries.data_ptr(), int(queries.shape[0]), rows.data_ptr(), offsets.data_ptr(),
+                                          counts.data_ptr(), int(total), scores.data_ptr(), err.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream), entry)
+    return scores, err
 
 
 def topk_desc_device(scores, k: int):

@@ -362,14 +362,7 @@ class DeviceVectors:
         epsilon) is left in ``last_search_stats``."""
         from ._exact import exact_top_k
 
-        shape = tuple(int(v) for v in getattr(queries, "shape", ())) or tuple(np.asarray(queries).shape)
-        if len(shape) != 2 or shape[1] != self.dim:
-            raise ValueError(f"Vectors must have shape (n, {self.dim}); received {shape}")
-        rows, row_ids = self._search_snapshot()
-        stats: Dict[str, Any] = {}
-        got = exact_top_k(queries, rows, k, row_ids=row_ids, method=method, return_tensors=return_tensors, stats=stats)
-        self.last_search_stats = stats
-        return got
+        return self._search(exact_top_k, queries, k, method=method, return_tensors=return_tensors)
 
     def search_above(self, queries, threshold, *, max_pairs: int = 1 << 26, return_tensors: bool = False):
         """Every stored vector at or above a cosine ``threshold`` (a number, or one per query) for every query, exactly, under
@@ -378,13 +371,17 @@ class DeviceVectors:
         (pairs the first pass let through, pairs kept, launches, epsilon) is left in ``last_search_stats``."""
         from ._exact import exact_above
 
+        return self._search(exact_above, queries, threshold, max_pairs=max_pairs, return_tensors=return_tensors)
+
+    def _search(self, fn, queries, what, **kwargs):
+        """``fn`` (``exact_top_k`` / ``exact_above``) of ``queries`` and ``what`` (its ``k`` / ``threshold``) over one snapshot
+        of the row block and its row -> id list; what it did goes to ``last_search_stats``."""
         shape = tuple(int(v) for v in getattr(queries, "shape", ())) or tuple(np.asarray(queries).shape)
         if len(shape) != 2 or shape[1] != self.dim:
             raise ValueError(f"Vectors must have shape (n, {self.dim}); received {shape}")
         rows, row_ids = self._search_snapshot()
         stats: Dict[str, Any] = {}
-        got = exact_above(queries, rows, threshold, row_ids=row_ids, max_pairs=max_pairs, return_tensors=return_tensors,
-                          stats=stats)
+        got = fn(queries, rows, what, row_ids=row_ids, stats=stats, **kwargs)
         self.last_search_stats = stats
         return got
 

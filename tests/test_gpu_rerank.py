@@ -209,3 +209,68 @@ def test_full_size_config3_properties():
         want = O.top_k_cosine(q_h[t], cand, k=1000)
         got = list(zip(order[qi].cpu().tolist(), scores[qi].cpu().tolist()))
         assert_same_ranking(got, want)
+
+
+@pytest.mark.parametrize("name", ["float32", "bfloat16", "float16", "int8", "float8_e4m3fn"])
+def test_ragged_wrapper_equals_the_batch_form_bit_for_bit(name):
+    """``cosine_ragged_device`` against ``cosine_scores_device`` on the same (query, row) pairs: one kernel behind both forms,
+    so the float32 bits agree.  37 rows of 70 elements (one 64-wide step and a tail) at a row stride of 72; three queries with
+    5, 0 and 9 candidates - the empty list moves the offsets - and rows that occur under more than one query."""
+    import torch
+
+    from lshrs_amd.similarity import cosine_ragged_device, cosine_scores_device, quantize_rows
+
+    m, ld, dim = 37, 72, 70
+    dt = getattr(torch, name)
+    gen = torch.Generator("cuda").manual_seed(70)
+    x = torch.randn(m, dim, device="cuda", generator=gen)
+    src = quantize_rows(x, dt) if dt.itemsize == 1 else x.to(dt)
+    store = torch.zeros(m, ld, dtype=dt, device="cuda")
+    store.view(torch.uint8)[:, :dim * dt.itemsize].copy_(src.contiguous().view(torch.uint8))
+    corpus = store[:, :dim]
+    assert corpus.stride(0) == ld and corpus.stride(1) == 1
+    queries = torch.randn(3, dim, device="cuda", generator=gen)
+    lists = [[0, 36, 17, 5, 20], [], [36, 5, 1, 2, 17, 30, 31, 0, 11]]
+    counts = [len(v) for v in lists]
+    total = sum(counts)
+    rows = torch.tensor([r for v in lists for r in v], dtype=torch.int64, device="cuda")
+    offsets = torch.tensor([0, 5, 5], dtype=torch.int64, device="cuda")
+    count_d = torch.tensor(counts, dtype=torch.int32, device="cuda")
+    padded = torch.full((3, max(counts)), -1, dtype=torch.int64, device="cuda")
+    valid = torch.zeros((3, max(counts)), dtype=torch.bool, device="cuda")
+    for i, v in enumerate(lists):
+        padded[i, :len(v)] = torch.tensor(v, dtype=torch.int64)
+        valid[i, :len(v)] = True
+
+    def bits(t):
+        return t.contiguous().view(torch.int32)
+
+    want, status, qstatus = cosine_scores_device(corpus, queries, padded)
+    assert status[valid].tolist() == [0] * total and status[~valid].tolist() == [2] * int((~valid).sum())
+    assert qstatus.tolist() == [0, 0, 0]
+    scores, err = cosine_ragged_device(corpus, queries, rows, offsets, count_d, total)
+    assert scores.shape == (total,) and scores.dtype == torch.float32 and err.dtype == torch.int32 and err.shape == (1,)
+    assert int(err.item()) == 0
+    assert torch.equal(bits(scores), bits(want[valid]))         # (row-major order of the mask = the order of the lists)
+    assert bool(torch.isfinite(scores).all()) and float(scores.abs().max()) <= 1.0 + 1e-6
+
+    # given outputs are the ones written: the scores land in the caller's tensor (nothing behind `total`), the report in its word
+    mine = torch.full((total + 2,), 7.0, dtype=torch.float32, device="cuda")
+    word = torch.zeros(1, dtype=torch.int32, device="cuda")
+    got = cosine_ragged_device(corpus, queries, rows, offsets, count_d, total, scores=mine, err=word)
+    assert got[0] is mine and got[1] is word
+    assert torch.equal(bits(mine[:total]), bits(scores)) and mine[total:].tolist() == [7.0, 7.0]
+    assert int(word.item()) == 0
+
+    # a zero row among the candidates (row 17: in the first and the last list): status 1 there in the batch form, bit 0 of err
+    # in the ragged one, NaN at its places in both, every other score as before
+    store.view(torch.uint8)[17] = 0
+    want0, status0, _ = cosine_scores_device(corpus, queries, padded)
+    zero = padded == 17
+    assert status0[zero].tolist() == [1, 1] and status0[valid & ~zero].tolist() == [0] * (total - 2)
+    scores0, err0 = cosine_ragged_device(corpus, queries, rows, offsets, count_d, total)
+    assert int(err0.item()) == 1
+    flat_zero = rows == 17
+    assert bool(torch.isnan(scores0[flat_zero]).all()) and bool(torch.isnan(want0[zero]).all())
+    assert torch.equal(bits(scores0[~flat_zero]), bits(want0[valid & ~zero]))
+    assert torch.equal(bits(scores0[~flat_zero]), bits(scores[~flat_zero]))
