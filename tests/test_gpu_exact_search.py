@@ -384,3 +384,82 @@ def test_lshrs_search_exact_and_recall():
         plain.search_exact(Q[:, :50], k)
     with pytest.raises(ValueError):
         plain.search_exact(Q, 0)
+
+
+@functools.lru_cache(maxsize=None)
+def _unplanted(dim):
+    """Gaussian rows and queries with no planted neighbours (made once, never modified)."""
+    rng = np.random.default_rng(2024 + dim)
+    X = rng.standard_normal((5000, dim)).astype(np.float32)
+    Q = rng.standard_normal((70, dim)).astype(np.float32)
+    return Q, X
+
+
+@functools.lru_cache(maxsize=None)
+def _unplanted_case(dim, name):
+    """The unplanted data in one stored form, with every query's float64 cosines of the stored rows in descending order
+    (computed once, never modified)."""
+    torch = _torch()
+    Q, X = _unplanted(dim)
+    stored = _stored_form(torch, name, X)
+    upcast = stored.float().cpu().numpy()
+    ranked = -np.sort(-np.stack([cosines_f64(Q[i], upcast) for i in range(Q.shape[0])]), axis=1)
+    for a in (upcast, ranked):
+        a.setflags(write=False)
+    return {"Q": Q, "stored": stored, "upcast": upcast, "ranked": ranked}
+
+
+@pytest.mark.parametrize("k,window", ((2, 4), (3, 8), (5, 16), (8, 16), (17, 64), (32, 64)))
+@pytest.mark.parametrize("name", DTYPES)
+@pytest.mark.parametrize("dim", (33, 100))
+def test_every_window_through_exact_top_k(dim, name, k, window):
+    """k of 2, 3, 5, 8, 17, 32: windows of 4, 8, 16, 16, 64, 64 - the widths between those the planted shapes reach, among them
+    the selection's middle form (windows 33 .. 64, any k of 17 .. 32).  The data is not planted; that the first pass must settle
+    every query is established from the data itself: every query's gap between its k-th and its window-th float64 cosine exceeds
+    three times what the settle rule charges (epsilon + the rerank's rounding), where twice is what the rule needs."""
+    from lshrs_amd import exact_top_k
+    from lshrs_amd._exact import choose_window, rerank_rounding, scan_epsilon, scan_max_window
+
+    case = _unplanted_case(dim, name)
+    Q, stored, up, ranked = case["Q"], case["stored"], case["upcast"], case["ranked"]
+    q, n = Q.shape[0], up.shape[0]
+    assert choose_window(k, scan_max_window()) == window
+    charged = scan_epsilon(stored.dtype, dim) + rerank_rounding(dim)
+    gap = float((ranked[:, k - 1] - ranked[:, window - 1]).min())
+    print(f"dim {dim} {name} k {k} window {window}: smallest gap {gap:.3e}, three times the charge {3 * charged:.3e}")
+    assert gap > 3 * charged, "the data does not let the first pass settle every query: take another seed"
+    stats = {}
+    ids, scores = exact_top_k(Q, stored, k, method="scan", stats=stats)
+    g_ids, g_scores = exact_top_k(Q, stored, k, method="gather")
+    assert np.array_equal(ids, g_ids) and np.array_equal(scores.view(np.uint32), g_scores.view(np.uint32))
+    _judge_all(ids, scores, _reference(Q, up, k), Q, np.arange(n), lambda c: up[np.asarray(c)])
+    assert stats["window"] == window and stats["settled_first_pass"] == q and stats["gathered"] == 0, stats
+
+
+@pytest.mark.parametrize("name", ("float32", "bfloat16"))
+def test_rows_that_are_not_finite_are_in_no_answer(name):
+    """A row holding a NaN or an infinity has no cosine: with k well below the number of finite rows it is in no answer, by
+    either method, and the two agree."""
+    torch = _torch()
+    from lshrs_amd import exact_top_k
+
+    Q, X = _unplanted(33)
+    X = X[:3000].copy()
+    rng = np.random.default_rng(6)
+    bad = rng.choice(3000, 9, replace=False)
+    for j, value in enumerate((np.nan, np.inf, -np.inf) * 3):
+        X[bad[j], rng.integers(0, 33)] = value
+    X[bad[0]] = np.nan                                      # (a row of nothing but NaN)
+    X[bad[1], :2] = (np.inf, -np.inf)
+    stored = _stored_form(torch, name, X)
+    assert int((~torch.isfinite(stored.float())).any(dim=1).sum()) == 9
+    up = stored.float().cpu().numpy()
+    fine = np.setdiff1d(np.arange(3000), bad)
+    for k in (1, 10, 32):
+        stats = {}
+        ids, scores = exact_top_k(Q, stored, k, method="scan", stats=stats)
+        g_ids, g_scores = exact_top_k(Q, stored, k, method="gather")
+        assert not set(bad.tolist()) & set(ids.reshape(-1).tolist()) and np.isfinite(scores).all()
+        assert np.array_equal(ids, g_ids) and np.array_equal(scores.view(np.uint32), g_scores.view(np.uint32))
+        want = [[(int(fine[p]), s) for p, s in row] for row in _reference(Q, up[fine], k)]
+        _judge_all(ids, scores, want, Q, fine, lambda c: up[np.asarray(c)])
