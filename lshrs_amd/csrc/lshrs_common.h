@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <math.h>
+#include <type_traits>
 
 #include "lshrs_hip.h"
 
@@ -319,7 +320,77 @@ __device__ __forceinline__ void deposit_abs_below(uint32_t& word, float y, float
       : "vcc");
 }
 
+// ------------------------------------------------------------------------------------------
+// What the signature kernels share: rules of stage 1, each stated once.  No state; values in, values out.  (Where a parameter
+// is a `const float&` DO NOT make it a value: hipcc then schedules sig16_kernel and sig16r_kernel differently - compare the assembly.)
+// ------------------------------------------------------------------------------------------
+// Row flags: bit 0 = a zero vector (largest |x| at most 1e-8), bit 1 = a NaN among the elements (s2: the sum of squares).
+__device__ __forceinline__ uint8_t row_flag_byte(float am, float s2) {
+  const bool has_nan = s2 != s2;
+  const bool zero = (am <= 1e-8f) && !has_nan;
+  return (uint8_t)((zero ? 1 : 0) | (has_nan ? 2 : 0));
+}
 
+// A 16-byte chunk at a row's end.  `part`: fetched from x[dim - 4 .. dim - 1], it holds the row's last rem = dim % 4 elements -
+// element e of the chunk is v[e + 4 - rem] for e < rem, zero behind them.  `gone`: wholly past the row's end, it reads as zero.
+__device__ __forceinline__ f32x4 tail_chunk(f32x4 v, int rem, bool part, bool gone) {
+  const float w0 = rem == 1 ? v[3] : (rem == 2 ? v[2] : v[1]);
+  const float w1 = rem == 1 ? 0.f : (rem == 2 ? v[3] : v[2]);
+  const float w2 = rem == 3 ? v[3] : 0.f;
+  f32x4 r = part ? f32x4{w0, w1, w2, 0.f} : v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) r[e] = gone ? 0.f : r[e];
+  return r;
+}
+
+// A row's statistics live in the four lanes r16 + 16 g of its row: their sum (||x_hi||^2, ||x_mid||^2), their maximum (|x|).  (const float&: see above)
+__device__ __forceinline__ float row_lanes_sum(const float& v) {
+  float s = v + __shfl_xor(v, 16);
+  s += __shfl_xor(s, 32);
+  return s;
+}
+__device__ __forceinline__ float row_lanes_max(const float& v) {
+  float m = __builtin_fmaxf(v, __shfl_xor(v, 16));
+  m = __builtin_fmaxf(m, __shfl_xor(m, 32));
+  return m;
+}
+
+// The two factors of a row's stage-1 window: |y1| <= window_hi * wa[col] + window_mid * wb[col] goes to stage 2.  s2, m2 sum the
+// very bf16 values the matrix instructions consumed (f32 accumulation: + 0.1 %, which also covers what separates ||x_hi|| +
+// ||x_mid|| from ||x||).  A largest |x| outside [2^-32, 2^32] leaves the range in which the squares and the split neither
+// underflow nor overflow: +inf, every projection of the row is re-evaluated (NaN / Inf rows: the second factor is 0).
+// RAW_ROOT: v_sqrt_f32 as it is (1 ulp), not the library's corrected root - each kernel keeps its own; 0.1 % covers either.
+template <bool RAW_ROOT>
+__device__ __forceinline__ float window_root(float v) { return RAW_ROOT ? __builtin_amdgcn_sqrtf(v) : sqrtf(v); }
+template <bool RAW_ROOT>
+__device__ __forceinline__ float window_hi(float s2, float am, float tau) {
+  float window = window_root<RAW_ROOT>(s2) * tau * 1.001f;
+  if (am != 0.f && !(am >= 0x1p-32f && am <= 0x1p32f)) window = __builtin_inff();
+  return window;
+}
+template <bool RAW_ROOT>
+__device__ __forceinline__ float window_mid(float m2, float tau_b) {
+  const float wb = window_root<RAW_ROOT>(m2) * tau_b * 1.001f;
+  return wb < __builtin_inff() ? wb : 0.f;
+}
+
+// A list entry: (row << kEntryColBits) | padded key column (sig_shape_ok bounds the columns)
+constexpr int kEntryColBits = 21;
+__host__ __device__ __forceinline__ int64_t flag_entry(int64_t row, int col) { return (row << kEntryColBits) | (int64_t)col; }
+__host__ __device__ __forceinline__ int64_t entry_row(int64_t entry) { return entry >> kEntryColBits; }
+__host__ __device__ __forceinline__ int entry_col(int64_t entry) { return (int)(entry & ((1 << kEntryColBits) - 1)); }
+
+// The stage-1 value travels with its entry: stage 2 measures |y1 - y_BLAS| on every flagged projection (rows flagged
+// wholesale - window = +inf - carry no usable y1: NaN, skipped by that statistic).  (const float&: see above)
+__device__ __forceinline__ float ykeep(const float& window, const float& y) { return window < __builtin_inff() ? y : __builtin_nanf(""); }
+
+// Key byte = bits [src, src + 8) of the row's sign string (lo: the word that holds bit src, hi: the one behind it), masked to
+// the band's live rows.  ALIGNBIT: v_alignbit instead of the 64-bit shift - each kernel keeps its instruction.
+template <bool ALIGNBIT>
+__device__ __forceinline__ uint32_t key_byte(uint32_t lo, uint32_t hi, int src, uint32_t mask) {
+  const uint32_t v = ALIGNBIT ? __builtin_amdgcn_alignbit(hi, lo, (uint32_t)(src & 31)) : (uint32_t)((((uint64_t)hi << 32) | lo) >> (src & 31));
+  return v & mask;
+}
 
 // ------------------------------------------------------------------------------------------
 // Stage 2 of the split-precision pass, for every flagged (row, padded column).  Without the replay it re-evaluates
@@ -372,6 +443,31 @@ struct FixArgs {
   int* overflow;
 };
 constexpr int kFixParts = 6;
+
+// What every stage-2 launch sets alike (split_pass, lshrs_sig_resolve_ties_replay_f32).  The tie window: tau units of
+// ||x|| ||p||, or (tau <= 0) the proven coefficient per column with factor 1.  The rest is the caller's.
+inline FixArgs fix_args_base(const float* X, int64_t ldx, int dim, const float* base, const SigGeom& g, int rows_per_band, uint8_t* keys,
+                             int row_bytes, const int64_t* flag_list, const int* flag_count, int flag_cap, float tau, int blas_model) {
+  FixArgs f{};
+  f.X = X;
+  f.ldx = ldx;
+  f.dim = dim;
+  f.ktiles = g.ktiles;
+  f.prow = base + sig_rowmajor_offset_floats(g);
+  f.norms = base + sig_image_floats(g);
+  f.keys = keys;
+  f.row_bytes = row_bytes;
+  f.padcols = row_bytes * 8;
+  f.flag_list = flag_list;
+  f.flag_count = flag_count;
+  f.flag_cap = flag_cap;
+  f.tau = tau > 0.f ? tau : 1.0f;
+  f.tie_coef = tau > 0.f ? f.norms : sig_window(base, g).wt;
+  f.blas_model = blas_model;
+  f.rows_per_band = rows_per_band;
+  f.band_cols = 8 * g.bb;
+  return f;
+}
 
 // The host BLAS's left-over rows (blas_row_kind != 0) multiply and add in TWO roundings: never contracted into an fma.
 __device__ __forceinline__ float mul_then_add(float acc, float a, float b) {
@@ -490,10 +586,16 @@ inline Opts read_opts(const lshrs_sig_opts* o) {
   }
   return r;
 }
+// A run-time flag as a compile-time one: f(std::true_type / std::false_type) - the launch ladders' rungs
+template <class F>
+inline void dispatch_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
 inline bool sig_shape_ok(int32_t num_bands, int32_t rows, int32_t dim) {
   if (num_bands <= 0 || rows <= 0 || dim <= 0) return false;
   const int64_t padcols = (int64_t)num_bands * ((rows + 7) / 8) * 8;
-  return padcols <= (1 << 21);
+  return padcols <= (1 << kEntryColBits);
 }
 
 }  // namespace lshrs

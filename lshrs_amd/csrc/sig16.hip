@@ -197,16 +197,8 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
       for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-          // the chunk with the row's last dim % 4 elements holds x[dim - 4 .. dim - 1]: element e is v[e + 4 - rem] for e < rem
-          const bool part = rem != 0 && 2 * g + c == lim;
-          const bool gone = 2 * g + c >= lim && !part;
-          const f32x4 v = xr[rt][c];
-          const float w0 = rem == 1 ? v[3] : (rem == 2 ? v[2] : v[1]);
-          const float w1 = rem == 1 ? 0.f : (rem == 2 ? v[3] : v[2]);
-          const float w2 = rem == 3 ? v[3] : 0.f;
-          xr[rt][c] = part ? f32x4{w0, w1, w2, 0.f} : v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) xr[rt][c][e] = gone ? 0.f : xr[rt][c][e];
+          const bool part = rem != 0 && 2 * g + c == lim;      // the chunk with the row's last dim % 4 elements
+          xr[rt][c] = tail_chunk(xr[rt][c], rem, part, 2 * g + c >= lim && !part);
         }
     }
   };
@@ -417,10 +409,8 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
   if (tid == 0) l_count[0] = 0;
 
   // ---- row statistics -> the two factors of the stage-1 window per row ------------------------------------------------
-  // ||x_hi|| and ||x_mid|| are sums over the very bf16 values the matrix instructions consumed (f32 accumulation: + 0.1 %,
-  // which also covers what separates ||x_hi|| + ||x_mid|| from ||x||).  A row whose largest |x| is outside
-  // [2^-32, 2^32] leaves the range in which the squares and the split neither underflow nor overflow: all of its
-  // projections are re-evaluated (NOT(|y| > +inf) holds for every y).  A true zero row gives y = 0 in both passes.
+  // (window_hi: a row outside the guarded range gets +inf - NOT(|y| > +inf) holds for every y: all of its projections are
+  // re-evaluated.  A true zero row gives y = 0 in both passes.)
   float* wnd_lds = lds + kWndOff + wave * kWaveRows;
   float* wnb_lds = lds + kWndOff + kRows + wave * kWaveRows;
   // the window coefficients of this column block, staged once (behind the list stage, which owns the first 3 x kS1ListCap
@@ -437,24 +427,12 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
   if (COMPACT && tid < 256) padcol_lds[tid] = args.padcol[cb * 256 + tid];
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
-    float s2 = ss[rt] + __shfl_xor(ss[rt], 16);
-    s2 += __shfl_xor(s2, 32);
-    float m2 = sm[rt] + __shfl_xor(sm[rt], 16);
-    m2 += __shfl_xor(m2, 32);
-    float am = __builtin_fmaxf(amax[rt], __shfl_xor(amax[rt], 16));
-    am = __builtin_fmaxf(am, __shfl_xor(am, 32));
+    const float s2 = row_lanes_sum(ss[rt]), m2 = row_lanes_sum(sm[rt]), am = row_lanes_max(amax[rt]);
     const int64_t myrow = row0 + 16 * rt + r16e;
     if (ge == 0) {
-      float window = sqrtf(s2) * args.tau * 1.001f;
-      if (am != 0.f && !(am >= 0x1p-32f && am <= 0x1p32f)) window = __builtin_inff();
-      wnd_lds[16 * rt + r16e] = window;
-      const float wb_ = sqrtf(m2) * args.tau_b * 1.001f;
-      wnb_lds[16 * rt + r16e] = wb_ < __builtin_inff() ? wb_ : 0.f;      // (NaN / Inf rows: the first factor decides)
-      if (cb == 0 && args.row_flags != nullptr && myrow < args.n) {
-        const bool has_nan = s2 != s2;
-        const bool zero = (am <= 1e-8f) && !has_nan;
-        args.row_flags[myrow] = (uint8_t)((zero ? 1 : 0) | (has_nan ? 2 : 0));
-      }
+      wnd_lds[16 * rt + r16e] = window_hi<false>(s2, am, args.tau);
+      wnb_lds[16 * rt + r16e] = window_mid<false>(m2, args.tau_b);
+      if (cb == 0 && args.row_flags != nullptr && myrow < args.n) args.row_flags[myrow] = row_flag_byte(am, s2);
     }
   }
   __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -536,15 +514,15 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
                 const int slot = atomicAdd(args.col_count + colid, 1);
                 if (slot < args.col_cap) {
                   const size_t at = (size_t)colid * args.col_cap + slot;
-                  args.tie_list[at] = ((grow << 21) | (int64_t)colid) | kAuditBit;
+                  args.tie_list[at] = flag_entry(grow, colid) | kAuditBit;
                   args.flag_y[at] = yq;
                   args.flag_thr[at] = tq;
                 }
               }
             } else {
-            args.audit_list[au_slot] = keep ? ((grow << 21) | (int64_t)colid) : (int64_t)-1;
-            args.audit_vals[2 * au_slot] = yq;
-            args.audit_vals[2 * au_slot + 1] = tq;
+              args.audit_list[au_slot] = keep ? flag_entry(grow, colid) : (int64_t)-1;
+              args.audit_vals[2 * au_slot] = yq;
+              args.audit_vals[2 * au_slot + 1] = tq;
             }
           }
           if (hits != 0u) {
@@ -557,26 +535,24 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
               //  them to stage 2, which skips them; a bucket launch has no segment for them)
               if (((hits >> q) & 1u) != 0u && grow < args.n && (!COMPACT || colid >= 0) &&
                   (args.col_cap == 0 || colid < args.row_bytes * 8)) {
-                const int64_t entry = (grow << 21) | (int64_t)colid;
-                // the stage-1 value travels with the entry: stage 2 measures |y1 - y_BLAS| on every flagged projection
-                // (rows flagged wholesale carry no usable y1: NaN, skipped by that statistic)
-                const float ykeep = wnd[reg] < __builtin_inff() ? ys[q] : __builtin_nanf("");
+                const int64_t entry = flag_entry(grow, colid);
+                const float yk = ykeep(wnd[reg], ys[q]);
                 const int pos = atomicAdd(l_count, 1);                    // LDS atomic
                 if (pos < kS1ListCap) {
                   l_list[pos] = entry;
-                  l_y[pos] = ykeep;
+                  l_y[pos] = yk;
                 } else if (args.col_cap > 0) {                            // LDS stage full, buckets: straight to the column's segment
                   atomicAdd(args.tie_count, 1);
                   const int slot = atomicAdd(args.col_count + colid, 1);
                   if (slot < args.col_cap) {
                     args.tie_list[(size_t)colid * args.col_cap + slot] = entry;
-                    args.flag_y[(size_t)colid * args.col_cap + slot] = ykeep;
+                    args.flag_y[(size_t)colid * args.col_cap + slot] = yk;
                   }
                 } else {                                                  // LDS stage full (rows flagged wholesale): straight out
                   const int slot = atomicAdd(args.tie_count, 1);
                   if (slot < args.tie_cap) {
                     args.tie_list[slot] = entry;
-                    if (args.flag_y != nullptr) args.flag_y[slot] = ykeep;
+                    if (args.flag_y != nullptr) args.flag_y[slot] = yk;
                   }
                 }
               }
@@ -628,8 +604,7 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
       if (grow < args.n) {
         const int src = tab[2 * o], w = src >> 5;
         const uint32_t lo = cw_lds[rl * 8 + w], hi = cw_lds[rl * 8 + (w < 7 ? w + 1 : 7)];
-        const uint32_t v = (uint32_t)((((uint64_t)hi << 32) | lo) >> (src & 31)) & (uint32_t)tab[2 * o + 1];
-        args.keys[grow * (int64_t)args.row_bytes + byte_base + o] = (uint8_t)v;
+        args.keys[grow * (int64_t)args.row_bytes + byte_base + o] = (uint8_t)key_byte<false>(lo, hi, src, (uint32_t)tab[2 * o + 1]);
       }
     }
   }
@@ -638,7 +613,7 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
     if (tid == 0) atomicAdd(args.tie_count, staged);    // one of <= 1024 addresses each: ~30 per workgroup at 768-d, ~60 at 1536-d)
     for (int e = tid; e < staged; e += 64 * W) {
       const int64_t entry = l_list[e];
-      const int col = (int)(entry & ((1 << 21) - 1));
+      const int col = entry_col(entry);
       const int slot = atomicAdd(args.col_count + col, 1);
       if (slot < args.col_cap) {
         args.tie_list[(size_t)col * args.col_cap + slot] = entry;
@@ -689,20 +664,12 @@ uint32_t lshrs_flags_sig16(void) {
 int lshrs_launch_sig16(const SigArgs& a, unsigned grid, bool compact, bool partial, bool half, hipStream_t s, hipEvent_t start,
                        hipEvent_t stop) {
   const dim3 g(grid, 1, 1), b(half ? 256 : 512, 1, 1);
-  if (half) {          // 128-row workgroups, two per CU (`grid` counts those)
-    if (compact) {
-      if (partial) hipExtLaunchKernelGGL((sig16_kernel<true, true, 4>), g, b, 0, s, start, stop, 0, a);
-      else hipExtLaunchKernelGGL((sig16_kernel<true, false, 4>), g, b, 0, s, start, stop, 0, a);
-    } else {
-      if (partial) hipExtLaunchKernelGGL((sig16_kernel<false, true, 4>), g, b, 0, s, start, stop, 0, a);
-      else hipExtLaunchKernelGGL((sig16_kernel<false, false, 4>), g, b, 0, s, start, stop, 0, a);
-    }
-  } else if (compact) {
-    if (partial) hipExtLaunchKernelGGL((sig16_kernel<true, true>), g, b, 0, s, start, stop, 0, a);
-    else hipExtLaunchKernelGGL((sig16_kernel<true, false>), g, b, 0, s, start, stop, 0, a);
-  } else {
-    if (partial) hipExtLaunchKernelGGL((sig16_kernel<false, true>), g, b, 0, s, start, stop, 0, a);
-    else hipExtLaunchKernelGGL((sig16_kernel<false, false>), g, b, 0, s, start, stop, 0, a);
-  }
+  dispatch_bool(half, [&](auto h) {          // (half: 128-row workgroups, two per CU - `grid` counts those)
+    dispatch_bool(compact, [&](auto c) {
+      dispatch_bool(partial, [&](auto p) {
+        hipExtLaunchKernelGGL((sig16_kernel<decltype(c)::value, decltype(p)::value, decltype(h)::value ? 4 : 8>), g, b, 0, s, start, stop, 0, a);
+      });
+    });
+  });
   return -(int)hipGetLastError();
 }

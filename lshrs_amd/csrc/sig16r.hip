@@ -161,16 +161,9 @@ __global__ __launch_bounds__(64 * res_waves(NCT, KT), 1) void sig16r_kernel(cons
           for (int c = 0; c < 2; ++c) {
             const int k0 = 32 * t + 8 * g + 4 * c;
             const bool gone = k0 >= dim;
-            if (rem != 0) {                                            // (uniform) the chunk with the row's last 1 .. 3 elements
-              const bool part = !gone && k0 + 4 > dim;                 // holds x[dim - 4 .. dim - 1]: element e is x[k0 + e]
-              const f32x4 v = xr[rt][t][c];                            // = v[e + 4 - rem] for e < rem, nothing behind it
-              const float w0 = rem == 1 ? v[3] : (rem == 2 ? v[2] : v[1]);
-              const float w1 = rem == 1 ? 0.f : (rem == 2 ? v[3] : v[2]);
-              const float w2 = rem == 3 ? v[3] : 0.f;
-              xr[rt][t][c] = part ? f32x4{w0, w1, w2, 0.f} : v;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) xr[rt][t][c][e] = gone ? 0.f : xr[rt][t][c][e];
+            // two calls, not one: the shift stays under its (uniform) branch - one call with both flags changes hipcc's code for this kernel
+            if (rem != 0) xr[rt][t][c] = tail_chunk(xr[rt][t][c], rem, !gone && k0 + 4 > dim, false);
+            xr[rt][t][c] = tail_chunk(xr[rt][t][c], rem, false, gone);
           }
       }
 #pragma unroll
@@ -237,23 +230,10 @@ __global__ __launch_bounds__(64 * res_waves(NCT, KT), 1) void sig16r_kernel(cons
     bool zrow[RT];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
-      float s2 = ss[rt] + __shfl_xor(ss[rt], 16);
-      s2 += __shfl_xor(s2, 32);
-      float m2 = sm[rt] + __shfl_xor(sm[rt], 16);
-      m2 += __shfl_xor(m2, 32);
-      float am = __builtin_fmaxf(amax[rt], __shfl_xor(amax[rt], 16));
-      am = __builtin_fmaxf(am, __shfl_xor(am, 32));
+      const float s2 = row_lanes_sum(ss[rt]), m2 = row_lanes_sum(sm[rt]), am = row_lanes_max(amax[rt]);
       const int64_t myrow = row0 + 16 * rt + r16;
-      // (v_sqrt_f32 as it is - 1 ulp - instead of the library's corrected root: the 0.1 % below covers far more)
-      float window = __builtin_amdgcn_sqrtf(s2) * args.tau * 1.001f;
-      if (am != 0.f && !(am >= 0x1p-32f && am <= 0x1p32f)) window = __builtin_inff();
-      float wb_ = __builtin_amdgcn_sqrtf(m2) * args.tau_b * 1.001f;
-      wb_ = wb_ < __builtin_inff() ? wb_ : 0.f;
-      if (g == 0 && args.row_flags != nullptr && myrow < args.n) {
-        const bool has_nan = s2 != s2;
-        const bool zero = (am <= 1e-8f) && !has_nan;
-        args.row_flags[myrow] = (uint8_t)((zero ? 1 : 0) | (has_nan ? 2 : 0));
-      }
+      const float window = window_hi<true>(s2, am, args.tau), wb_ = window_mid<true>(m2, args.tau_b);
+      if (g == 0 && args.row_flags != nullptr && myrow < args.n) args.row_flags[myrow] = row_flag_byte(am, s2);
       wnd[rt] = window;
       wnb[rt] = wb_;
       float ts = window < __builtin_inff() ? window * amax_cb + wb_ * bmax_cb : __builtin_inff();
@@ -324,7 +304,7 @@ __global__ __launch_bounds__(64 * res_waves(NCT, KT), 1) void sig16r_kernel(cons
               }
               const int colid = padcol_lds[16 * (2 * w + (au_q >> 2)) + 4 * g + (au_q & 3)];
               const bool keep = ((hits >> au_q) & 1u) == 0u && grow < args.n && colid >= 0 && tq < __builtin_inff();
-              args.audit_list[au_slot] = keep ? ((grow << 21) | (int64_t)colid) : (int64_t)-1;
+              args.audit_list[au_slot] = keep ? flag_entry(grow, colid) : (int64_t)-1;
               args.audit_vals[2 * au_slot] = yq;
               args.audit_vals[2 * au_slot + 1] = tq;
             }
@@ -334,17 +314,17 @@ __global__ __launch_bounds__(64 * res_waves(NCT, KT), 1) void sig16r_kernel(cons
                 const int reg = q & 3, ct = 2 * w + (q >> 2);
                 const int colid = padcol_lds[16 * ct + 4 * g + reg];
                 if (((hits >> q) & 1u) != 0u && grow < args.n && colid >= 0) {
-                  const int64_t entry = (grow << 21) | (int64_t)colid;
-                  const float ykeep = wnd[rt] < __builtin_inff() ? ys[q] : __builtin_nanf("");
+                  const int64_t entry = flag_entry(grow, colid);
+                  const float yk = ykeep(wnd[rt], ys[q]);
                   const int pos = atomicAdd(l_count, 1);                  // LDS atomic on the wave's own counter
                   if (pos < kResListCap) {
                     l_list[pos] = entry;
-                    l_y[pos] = ykeep;
+                    l_y[pos] = yk;
                   } else {                                                // the wave's stage is full (rows flagged wholesale)
                     const int slot = atomicAdd(args.tie_count, 1);
                     if (slot < args.tie_cap) {
                       args.tie_list[slot] = entry;
-                      if (args.flag_y != nullptr) args.flag_y[slot] = ykeep;
+                      if (args.flag_y != nullptr) args.flag_y[slot] = yk;
                     }
                   }
                 }
@@ -377,8 +357,7 @@ __global__ __launch_bounds__(64 * res_waves(NCT, KT), 1) void sig16r_kernel(cons
         for (int b = 0; b < 4; ++b) {
           const int src = (int)(rec[b] & 0xFFFFu), w = src >> 5;
           const uint32_t lo = cw_lds[rl * 9 + w], hi_ = cw_lds[rl * 9 + w + 1];    // (a ninth word per row: never live, always readable)
-          const uint32_t v = __builtin_amdgcn_alignbit(hi_, lo, (uint32_t)(src & 31)) & (rec[b] >> 16);
-          out |= v << (8 * b);
+          out |= key_byte<true>(lo, hi_, src, rec[b] >> 16) << (8 * b);
         }
 #ifdef LSHRS_AB_RES_NO_KEYSTORE     // (A/B builds only: what the key stores cost the waves' load waits - one word per launch keeps the work alive)
         if (out == 0x12345678u && row0 + rl < args.n) *reinterpret_cast<uint32_t*>(args.keys + (row0 + rl) * (int64_t)nby + 4 * o4) = out;
@@ -392,8 +371,7 @@ __global__ __launch_bounds__(64 * res_waves(NCT, KT), 1) void sig16r_kernel(cons
         const uint32_t rec = (uint32_t)tab_lds[o];
         const int src = (int)(rec & 0xFFFFu), w = src >> 5;
         const uint32_t lo = cw_lds[rl * 9 + w], hi_ = cw_lds[rl * 9 + w + 1];
-        const uint32_t v = __builtin_amdgcn_alignbit(hi_, lo, (uint32_t)(src & 31)) & (rec >> 16);
-        if (row0 + rl < args.n) args.keys[(row0 + rl) * (int64_t)nby + o] = (uint8_t)v;
+        if (row0 + rl < args.n) args.keys[(row0 + rl) * (int64_t)nby + o] = (uint8_t)key_byte<true>(lo, hi_, src, rec >> 16);
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -471,17 +449,26 @@ uint32_t lshrs_flags_sig16r(void) {
   return f;
 }
 
+template <int NCT, int KT>
+static void launch_res_one(const SigArgs& a, dim3 grid, dim3 block, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+  hipExtLaunchKernelGGL((sig16r_kernel<NCT, KT>), grid, block, 0, s, start, stop, 0, a);
+}
+// nct is 4, 8, 12 or 16 column tiles; with eight k-tiles only 4 and 8 exist (sig_resident: nct x kt <= 64): there anything but 4 is 8
+template <int KT>
+static void launch_res(int nct, const SigArgs& a, dim3 grid, dim3 block, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+  if (nct == 4) launch_res_one<4, KT>(a, grid, block, s, start, stop);
+  else if (nct == 8 || KT == 8) launch_res_one<8, KT>(a, grid, block, s, start, stop);
+  else if constexpr (KT != 8) {
+    if (nct == 12) launch_res_one<12, KT>(a, grid, block, s, start, stop);
+    else launch_res_one<16, KT>(a, grid, block, s, start, stop);
+  }
+}
+
 int lshrs_launch_sig16r(const SigArgs& a, int nct, int kt, unsigned grid_x, unsigned block_x, hipStream_t s, hipEvent_t start,
                         hipEvent_t stop) {
   const dim3 grid(grid_x, 1, 1), block(block_x, 1, 1);
-#define LSHRS_RES(NCT_, KT_) hipExtLaunchKernelGGL((sig16r_kernel<NCT_, KT_>), grid, block, 0, s, start, stop, 0, a)
-  if (kt == 2) {
-    if (nct == 4) LSHRS_RES(4, 2); else if (nct == 8) LSHRS_RES(8, 2); else if (nct == 12) LSHRS_RES(12, 2); else LSHRS_RES(16, 2);
-  } else if (kt == 4) {
-    if (nct == 4) LSHRS_RES(4, 4); else if (nct == 8) LSHRS_RES(8, 4); else if (nct == 12) LSHRS_RES(12, 4); else LSHRS_RES(16, 4);
-  } else {
-    if (nct == 4) LSHRS_RES(4, 8); else LSHRS_RES(8, 8);
-  }
-#undef LSHRS_RES
+  if (kt == 2) launch_res<2>(nct, a, grid, block, s, start, stop);
+  else if (kt == 4) launch_res<4>(nct, a, grid, block, s, start, stop);
+  else launch_res<8>(nct, a, grid, block, s, start, stop);
   return -(int)hipGetLastError();
 }

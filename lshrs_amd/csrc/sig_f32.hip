@@ -180,9 +180,7 @@ __global__ __launch_bounds__(kSigWaves * 64, 2) void sig_kernel(const SigArgs ar
     if (h == 0) {
       norm_lds[i] = sqrtf(s2) * args.tau;
       if (cb == 0 && args.row_flags != nullptr && myrow < args.n) {
-        const bool has_nan = s2 != s2;
-        const bool zero = (am <= 1e-8f) && !has_nan;
-        args.row_flags[myrow] = (uint8_t)((zero ? 1 : 0) | (has_nan ? 2 : 0));
+        args.row_flags[myrow] = row_flag_byte(am, s2);
       }
     }
   }

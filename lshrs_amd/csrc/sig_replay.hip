@@ -20,11 +20,6 @@ __device__ __forceinline__ void fix_chain_tile(const f32x4 (&p4)[2][4], const f3
   }
 }
 
-// EIGHT flagged projections per wave.  One wave per projection (the first version of this kernel) has all 64 lanes
-// issue the same 2 x dim dependent fmas: at ~5 700 flagged projections per 262 144-row chunk that is 5-6 waves per
-// SIMD x 6 k issue cycles, i.e. the kernel is bound by redundant VALU issue (measured 33 us per chunk).  Here lane
-// (sub, g) = (lane >> 3, lane & 7) works for projection g of the wave's group: the eight 16-byte chunks (sub) of a
-
 // The library's scalar tail: the dim % 4 elements behind the last group of four are added in plain C behind all blocks
 // (lshrs_tb_model_row_dot) - tail_model 1 as OpenBLAS's SkylakeX build contracts that C, 2 as its Haswell / Zen build leaves it.
 // pt / xt: the first tail element of the hyperplane / the row; returns y with the tail, adds the tail's x^2 to *ss where asked.
@@ -47,6 +42,12 @@ __device__ __forceinline__ float blas_scalar_tail(float y, const float* __restri
 }
 
 static_assert(LSHRS_SIG_COUNTERS + kFixParts * kFixGridG <= LSHRS_SIG_DEVICE_COUNTERS, "stage 2's per-workgroup slots must fit the counter block");
+//
+// EIGHT flagged projections per wave.  One wave per projection (the first version of this kernel) has all 64 lanes
+// issue the same 2 x dim dependent fmas: at ~5 700 flagged projections per 262 144-row chunk that is 5-6 waves per
+// SIMD x 6 k issue cycles, i.e. the kernel is bound by redundant VALU issue (measured 33 us per chunk).  Here lane
+// (sub, g) = (lane >> 3, lane & 7) works for projection g of the wave's group: the eight 16-byte chunks (sub) of a
+// k-tile of x row g and of hyperplane column g go HBM/L2 -> LDS by LDS-DMA (lshrs_common.h, kFixG: the layout and the slabs).
 //
 // REPLAY: the tie-break on the device.  Every flagged projection gets the sign of the value the HOST BLAS computes for
 // it - the reference's `projection @ vector` (lshrs/hash/lsh.py:200) - and only that value is computed, by replaying
@@ -157,8 +158,8 @@ __global__ __launch_bounds__(64) void sig_fix8_kernel(const FixArgs a) {
       inlist = item >= 0;
       if (!inlist) item = 0;                         // (an empty slot: row 0, column 0 - fetched, never used)
     }
-    it.row = item >> 21;                            // relative to this launch's X / keys
-    const int col_raw = (int)(item & ((1 << 21) - 1));
+    it.row = entry_row(item);                            // relative to this launch's X / keys
+    const int col_raw = entry_col(item);
     it.live = inlist && col_raw < a.padcols;
     it.col = col_raw < a.padcols ? col_raw : 0;
     it.xrow = a.X + it.row * a.ldx;
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(64) void sig_fix8_kernel(const FixArgs a) {
     it.pg = a.prow + (size_t)it.col * ldp + head + 16 * shh + 4 * sq;
 #ifdef LSHRS_AB_FIX_SAME_P        // (A/B builds only: what a list sorted by column would make of the hyperplane stream - wrong keys by design)
     {
-      const int c0 = (int)(a.flag_list[grp * kFixG < cnt ? grp * kFixG : 0] & ((1 << 21) - 1));
+      const int c0 = entry_col(a.flag_list[grp * kFixG < cnt ? grp * kFixG : 0]);
       it.pg = a.prow + (size_t)(c0 < a.padcols ? c0 : 0) * ldp + 16 * shh + 4 * sq;
     }
 #endif
@@ -389,7 +390,7 @@ __global__ __launch_bounds__(64) void sig_fix8_kernel(const FixArgs a) {
 }
 
 // Tie entries of the f32 kernel, (row * 65536 + word, mask of up to 32 columns), unpacked into the stage-2 list format
-// (row << 21 | padded column), one item per flagged column: what sig_fix8_kernel<true> takes.
+// (flag_entry: row, padded column), one item per flagged column: what sig_fix8_kernel<true> takes.
 __global__ void expand_ties_kernel(const int64_t* __restrict__ tie_list, const int* __restrict__ tie_count, int tie_cap,
                                    int padcols, int64_t* __restrict__ flag_list, int flag_cap, int* flag_count) {
   const int cnt = min(*tie_count, tie_cap);
@@ -404,8 +405,8 @@ __global__ void expand_ties_kernel(const int64_t* __restrict__ tie_list, const i
       const int c = __ffs(mask) - 1;
       mask &= mask - 1u;
       const int col = 32 * word + c;
-      if (slot < flag_cap && col < padcols) flag_list[slot] = (row << 21) | (int64_t)col;
-      else if (slot < flag_cap) flag_list[slot] = (row << 21) | (int64_t)((1 << 21) - 1);   // (skipped by stage 2: column out of range)
+      if (slot < flag_cap && col < padcols) flag_list[slot] = flag_entry(row, col);
+      else if (slot < flag_cap) flag_list[slot] = flag_entry(row, (1 << kEntryColBits) - 1);   // (skipped by stage 2: column out of range)
       ++slot;
     }
   }
@@ -501,8 +502,8 @@ __global__ __launch_bounds__(64) void sig_fixany_kernel(const FixArgs a) {
       inlist = item >= 0;
       if (!inlist) item = 0;                                        // (an empty slot: row 0, column 0 - fetched, never used)
     }
-    const int64_t row = item >> 21;
-    const int col_raw = (int)(item & ((1 << 21) - 1));
+    const int64_t row = entry_row(item);
+    const int col_raw = entry_col(item);
     const bool live = inlist && col_raw < a.padcols;
     const int col = col_raw < a.padcols ? col_raw : 0;
     const float* __restrict__ xr = a.X + row * a.ldx;
@@ -652,8 +653,8 @@ __global__ __launch_bounds__(64) void sig_fixany_kernel(const FixArgs a) {
   }
 }
 
-// Behind stage 2 of a replay pass: folds the per-workgroup statistics (nparts slots of 3 ints behind the
-// LSHRS_SIG_COUNTERS counters: ties, sign flips, max deviation) into the counters, hands the counters to the host (pinned
+// Behind stage 2 of a replay pass: folds the per-workgroup statistics (nparts slots of kFixParts ints behind the
+// LSHRS_SIG_COUNTERS counters: FixArgs::partials) into the counters, hands the counters to the host (pinned
 // memory) and leaves the whole block zeroed for the next call: one small launch instead of a copy and a fill.
 // Without host_counts the folded counters stay in the device block (the caller copies it).
 constexpr int kExportThreads = 1024;      // one part or two per thread: the fold is one memory round trip deep, not nparts / 64
@@ -742,6 +743,14 @@ uint32_t lshrs_flags_replay(void) {
   return f;
 }
 
+// sig_fix8_kernel<true, GENERAL, SLAB, SAMEP>: GENERAL is picked here, once
+template <int SLAB, bool SAMEP>
+static void launch_replay(bool general, dim3 grid, const FixArgs& f, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+  dispatch_bool(general, [&](auto gen) {
+    hipExtLaunchKernelGGL((sig_fix8_kernel<true, decltype(gen)::value, SLAB, SAMEP>), grid, dim3(64), 0, s, start, stop, 0, f);
+  });
+}
+
 // Stage 2 of a split pass behind its stage 1 (sig_split.hip: split_pass), on stream s: the flagged projections of f.flag_list,
 // one by one.  blas_model 0: the canonical f32 chain, ties reported in f.tie_list.  > 0: the host BLAS's order replayed, keys
 // patched, the audit sample verified, the statistics folded into `counters` and handed to `host_counts`; where the caller
@@ -751,6 +760,7 @@ int lshrs_replay_stage2(const FixArgs& f, int32_t* counters, int32_t* host_count
   const int64_t* flag_list = f.flag_list;
   const float* flag_y = f.flag_y;
   const int* flag_count = f.flag_count;
+  const bool general = blas_general(rows_per_band, f.ktiles, dim);
   const int64_t groups = ((int64_t)flag_cap + kFixG - 1) / kFixG;
   const bool short_rows = f.ktiles <= kFixSlabShort && blas_model != 0;
   const int grid_cap = short_rows ? kFixGridShort : kFixGridG;
@@ -766,10 +776,7 @@ int lshrs_replay_stage2(const FixArgs& f, int32_t* counters, int32_t* host_count
       hipExtLaunchKernelGGL(sig_fixany_kernel, ogrid, block, 0, s, o.ev[2], o.ev[3], 0, f);
       nparts = (int)ogrid.x;
     } else if (short_rows) {
-      if (blas_general(rows_per_band, f.ktiles, dim))
-        hipExtLaunchKernelGGL((sig_fix8_kernel<true, true, kFixSlabShort>), grid, block, 0, s, o.ev[2], o.ev[3], 0, f);
-      else
-        hipExtLaunchKernelGGL((sig_fix8_kernel<true, false, kFixSlabShort>), grid, block, 0, s, o.ev[2], o.ev[3], 0, f);
+      launch_replay<kFixSlabShort, false>(general, grid, f, s, o.ev[2], o.ev[3]);
     } else if (f.col_cap > 0) {
       // BUCKETS: stage 1 left every flagged (and sampled) projection in its column's segment - stage 2 with ONE hyperplane per
       // group of eight at once, no sort, no launch of its own for the audit sample; the launch behind it also clears the
@@ -788,17 +795,13 @@ int lshrs_replay_stage2(const FixArgs& f, int32_t* counters, int32_t* host_count
       fb.audit_list = nullptr;
       fb.audit_n = 0;
       fb.overflow = counters + 7;
-      if (blas_general(rows_per_band, f.ktiles, dim))
-        hipExtLaunchKernelGGL((sig_fix8_kernel<true, true, kBucketSlab, true>), bgrid, block, 0, s, o.ev[2], o.ev[3], 0, fb);
-      else
-        hipExtLaunchKernelGGL((sig_fix8_kernel<true, false, kBucketSlab, true>), bgrid, block, 0, s, o.ev[2], o.ev[3], 0, fb);
+      launch_replay<kBucketSlab, true>(general, bgrid, fb, s, o.ev[2], o.ev[3]);
       hipLaunchKernelGGL(export_counts_kernel, dim3(1), dim3(kExportThreads), 0, s, counters, host_counts, (int)bgrid.x,
                          o.sort->hist + (size_t)(1 - (o.sort->parity & 1)) * kSortMaxCols, kSortMaxCols, o.done, o.epoch);
       return -(int)hipGetLastError();
-    } else if (blas_general(rows_per_band, f.ktiles, dim))
-      hipExtLaunchKernelGGL((sig_fix8_kernel<true, true>), grid, block, 0, s, o.ev[2], o.ev[3], 0, f);
-    else
-      hipExtLaunchKernelGGL((sig_fix8_kernel<true, false>), grid, block, 0, s, o.ev[2], o.ev[3], 0, f);
+    } else {
+      launch_replay<kFixSlabG, false>(general, grid, f, s, o.ev[2], o.ev[3]);
+    }
     hipLaunchKernelGGL(export_counts_kernel, dim3(1), dim3(kExportThreads), 0, s, counters, host_counts, nparts, nullptr, 0, o.done,
                        o.epoch);
   } else {
@@ -845,36 +848,15 @@ int lshrs_sig_resolve_ties_replay_f32(const float* X, int64_t n, int64_t ldx, co
     hipLaunchKernelGGL(expand_ties_kernel, dim3((unsigned)blocks), dim3(threads), 0, s, tie_list, tie_count, tie_cap,
                        row_bytes * 8, flag_list, flag_cap, flag_count);
   }
-  FixArgs f{};
-  f.X = X;
-  f.ldx = ldx;
-  f.dim = dim;
-  f.ktiles = g.ktiles;
-  f.prow = base + sig_rowmajor_offset_floats(g);
-  f.norms = base + sig_image_floats(g);
-  f.keys = keys;
-  f.row_bytes = row_bytes;
-  f.padcols = row_bytes * 8;
-  f.flag_list = flag_list;
-  f.flag_count = flag_count;
-  f.flag_cap = flag_cap;
-  f.row_base = 0;
-  f.tie_list = nullptr;
-  f.tie_cap = 0;
-  f.tie_count = nullptr;          // (the caller has the number of tie entries already; stage 2 only decides them)
-  f.tau = tau > 0.f ? tau : 1.0f;
-  f.tie_coef = tau > 0.f ? f.norms : sig_window(base, g).wt;
-  f.blas_model = blas_model;
-  f.rows_per_band = rows_per_band;
-  f.band_cols = 8 * g.bb;
+  // (no tie list: the caller has the number of tie entries already; stage 2 only decides them)
+  FixArgs f = fix_args_base(X, ldx, dim, base, g, rows_per_band, keys, row_bytes, flag_list, flag_count, flag_cap, tau, blas_model);
   f.partials = counters + LSHRS_SIG_COUNTERS;
   {
     const int64_t groups = ((int64_t)flag_cap + kFixG - 1) / kFixG;
     const dim3 grid((unsigned)(groups < kFixGridG ? groups : kFixGridG)), block(64);
     f.tail_model = blas_model;
     if (!fast || short_last_block) hipLaunchKernelGGL(sig_fixany_kernel, grid, block, 0, s, f);
-    else if (blas_general(rows_per_band, g.ktiles, dim)) hipLaunchKernelGGL((sig_fix8_kernel<true, true>), grid, block, 0, s, f);
-    else hipLaunchKernelGGL((sig_fix8_kernel<true, false>), grid, block, 0, s, f);
+    else launch_replay<kFixSlabG, false>(blas_general(rows_per_band, g.ktiles, dim), grid, f, s, nullptr, nullptr);
     hipLaunchKernelGGL(export_counts_kernel, dim3(1), dim3(kExportThreads), 0, s, counters, host_counts, (int)grid.x);
   }
   return -(int)hipGetLastError();

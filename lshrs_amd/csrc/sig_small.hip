@@ -118,9 +118,7 @@ __global__ __launch_bounds__(64) void sig_small_kernel(const SmallArgs a) {
   if (lane == 0) {
     a.keys[(int64_t)row * a.row_bytes + byte] = (uint8_t)bits;
     if (byte == 0 && a.row_flags != nullptr) {
-      const bool has_nan = s2 != s2;
-      const bool zero = (m2 <= 1e-8f) && !has_nan;
-      a.row_flags[row] = (uint8_t)((zero ? 1 : 0) | (has_nan ? 2 : 0));
+      a.row_flags[row] = row_flag_byte(m2, s2);
     }
     if (nt != 0) atomicAdd(a.counters, nt);
     if (a.host_done != nullptr) {

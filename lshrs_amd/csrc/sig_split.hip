@@ -110,57 +110,54 @@ static int split_pass(const float* X, int64_t n, int64_t ldx, const void* worksp
   a.ldx = ldx;
   a.dim = dim;
   a.ktiles = g.ktiles;
-  a.ncb = g.cb;
-  a.image = base + sig_t16_offset_floats(g);
-  a.norms = base + sig_image_floats(g);
-  a.norm_max = a.norms + sig_norm_floats(g);
-  if (narrow) {   // the zero-padded 256-column image and its norms
-    a.ncb = 1;
-    a.image = base + sig_narrow_offset_floats(g);
-    a.norms = a.image + sig_narrow_image_floats(g);
-    a.norm_max = a.norms + 256;
-  }
+  // its tables, for exactly one of four layouts: the resident image (sig16r_kernel) or compact column blocks (sig_compact) - list
+  // entries and keys leave through padcol / bytetab -, the narrow hasher's zero-padded 256-column block, the padded layout
   const SigCompact cp = sig_compact(g, num_bands, rows_per_band);
-  const SigCompactWs cw = cp.on ? sig_compact_ws(const_cast<float*>(base), g, cp) : SigCompactWs{};
-  if (cp.on) {    // fewer column blocks with the bands' columns side by side (sig_compact)
-    a.ncb = cp.ncb;
-    a.image = cw.image;
-    a.norms = cw.norms;
-    a.norm_max = cw.norm_max;
+  if (rs.on || cp.on) {
+    float* wbase = const_cast<float*>(base);
+    const SigCompactWs t = rs.on ? sig_resident_ws(wbase, g, num_bands, rows_per_band, rs) : sig_compact_ws(wbase, g, cp);
+    a.ncb = rs.on ? 1 : cp.ncb;
+    a.image = t.image;
+    a.norms = t.norms;
+    a.norm_max = t.norm_max;
+    a.wa = t.wa;
+    a.wb = t.wb;
+    a.wamax = t.wamax;
+    a.wbmax = t.wbmax;
     a.compact = 1;
-    a.padcol = cw.padcol;
-    a.bytetab = cw.bytetab;
-    a.bpb = cp.bpb;
+    a.padcol = t.padcol;
+    a.bytetab = t.bytetab;
+    a.bpb = rs.on ? num_bands : cp.bpb;
     a.band_bytes = g.bb;
     a.num_bands = num_bands;
+  } else {
+    const SigWindow w = sig_window(base, g);
+    a.ncb = narrow ? 1 : g.cb;
+    a.image = base + (narrow ? sig_narrow_offset_floats(g) : sig_t16_offset_floats(g));
+    a.norms = narrow ? a.image + sig_narrow_image_floats(g) : base + sig_image_floats(g);
+    a.norm_max = a.norms + (narrow ? 256 : sig_norm_floats(g));
+    a.wa = w.wa;
+    a.wb = w.wb;
+    a.wamax = narrow ? w.wamax + kNarrowMaxSlot : w.wamax;
+    a.wbmax = narrow ? w.wbmax + kNarrowMaxSlot : w.wbmax;
+  }
+  // the window: LSHRS_WINDOW_PROVEN - ||x_hi|| wa + ||x_mid|| wb (lshrs_sig_set_window) -, or tau1 units of ||x|| ||p|| (the caller's)
+  a.tau = a.tau_b = 1.0f;
+  if (tau1 > 0.f) {
+    a.tau = tau1;
+    a.tau_b = 0.f;
+    a.wa = a.wb = a.norms;
+    a.wamax = a.wbmax = a.norm_max;
   }
   a.keys = keys;
   a.row_bytes = row_bytes;
-  a.vec_store = (row_bytes % 16 == 0) && ((reinterpret_cast<uintptr_t>(keys) % 16) == 0);
+  const int key_align = rs.on ? 4 : 16;                 // (sig16r_kernel stores 32-bit words, sig16_kernel pairs of them)
+  a.vec_store = (row_bytes % key_align == 0) && ((reinterpret_cast<uintptr_t>(keys) % key_align) == 0);
   a.row_base = 0;
   a.tie_list = flag_list;
   a.flag_y = flag_y;
   a.tie_cap = flag_cap;
   a.tie_count = flag_count;
-  if (tau1 > 0.f) {                 // a window of tau1 units of ||x|| ||p||, the caller's responsibility
-    a.tau = tau1;
-    a.tau_b = 0.f;
-    a.wa = a.wb = a.norms;
-    a.wamax = a.wbmax = a.norm_max;
-  } else {                          // LSHRS_WINDOW_PROVEN: ||x_hi|| wa + ||x_mid|| wb (lshrs_sig_set_window)
-    const SigWindow w = sig_window(base, g);
-    a.tau = a.tau_b = 1.0f;
-    a.wa = w.wa;
-    a.wb = w.wb;
-    a.wamax = narrow ? w.wamax + kNarrowMaxSlot : w.wamax;
-    a.wbmax = narrow ? w.wbmax + kNarrowMaxSlot : w.wbmax;
-    if (cp.on) {
-      a.wa = cw.wa;
-      a.wb = cw.wb;
-      a.wamax = cw.wamax;
-      a.wbmax = cw.wbmax;
-    }
-  }
   a.row_flags = row_flags;
   a.clock_probe = o.clock_probe;
   // sig16_kernel's workgroup: 256 rows, or 128 (two per CU) - sig16_half_rows
@@ -198,27 +195,6 @@ static int split_pass(const float* X, int64_t n, int64_t ldx, const void* worksp
     a.col_cap = o.sort->cap / padcols_all;
   }
   if (rs.on) {
-    const SigCompactWs rw = sig_resident_ws(const_cast<float*>(base), g, num_bands, rows_per_band, rs);
-    a.ncb = 1;
-    a.image = rw.image;
-    a.norms = rw.norms;
-    a.norm_max = rw.norm_max;
-    a.compact = 1;
-    a.padcol = rw.padcol;
-    a.bytetab = rw.bytetab;
-    a.bpb = num_bands;
-    a.band_bytes = g.bb;
-    a.num_bands = num_bands;
-    a.vec_store = (row_bytes % 4 == 0) && ((reinterpret_cast<uintptr_t>(keys) % 4) == 0);
-    if (tau1 > 0.f) {
-      a.wa = a.wb = a.norms;
-      a.wamax = a.wbmax = a.norm_max;
-    } else {
-      a.wa = rw.wa;
-      a.wb = rw.wb;
-      a.wamax = rw.wamax;
-      a.wbmax = rw.wbmax;
-    }
     const int res_rows = 16 * res_rt(rs.nct, rs.kt);
     const int64_t tiles = (n + res_rows - 1) / res_rows;
     const int rwaves = res_waves(rs.nct, rs.kt);
@@ -233,28 +209,14 @@ static int split_pass(const float* X, int64_t n, int64_t ldx, const void* worksp
     if (rc != 0) return rc;
   }
   // stage 2: the flagged projections, one by one
-  FixArgs f{};
-  f.X = X;
-  f.ldx = ldx;
-  f.dim = dim;
-  f.ktiles = g.ktiles;
-  f.prow = base + sig_rowmajor_offset_floats(g);
-  f.norms = (cp.on || rs.on) ? base + sig_image_floats(g) : a.norms;       // (stage 2 works on padded column ids throughout)
-  f.keys = keys;
-  f.row_bytes = row_bytes;
-  f.padcols = row_bytes * 8;
-  f.flag_list = flag_list;
-  f.flag_count = flag_count;
-  f.flag_cap = flag_cap;
-  f.row_base = 0;
+  FixArgs f = fix_args_base(X, ldx, dim, base, g, rows_per_band, keys, row_bytes, flag_list, flag_count, flag_cap, tau, blas_model);
+  if (narrow && !rs.on) {          // (the narrow block's own copy of the norms: the same values for every valid column)
+    f.norms = a.norms;
+    if (tau > 0.f) f.tie_coef = f.norms;
+  }
   f.tie_list = tie_list;
   f.tie_cap = tie_cap;
   f.tie_count = tie_count;
-  f.tau = tau > 0.f ? tau : 1.0f;
-  f.tie_coef = tau > 0.f ? f.norms : sig_window(base, g).wt;      // (proven tie window: coefficient per column, factor 1)
-  f.blas_model = blas_model;
-  f.rows_per_band = rows_per_band;
-  f.band_cols = 8 * g.bb;
   if (buckets) {
     f.sorted_list = o.sort->list;
     f.sorted_y = o.sort->y;
