@@ -162,6 +162,14 @@ __host__ __device__ inline int res_colmap(int nct, int ct, int m) {
   const int bits = 4 * (nct - 8 * k < 8 ? nct - 8 * k : 8);
   return 128 * k + bits * g + (bits - 1) - (4 * (ct & 7) + e);
 }
+// The same rule for sig16_kernel's 256-column blocks (sixteen column tiles, padded, narrow and compact images alike): the
+// lane's two groups of eight column tiles land in NEIGHBOURING words 2 g, 2 g + 1 of the block's sign string, so that a lane
+// stores its 64 bits of a row as one pair of words.  Image position (ct, m) of a block holds the block's column t16_colmap(ct, m);
+// what stage 1 reads per image position (coefficients, padded column ids) is gathered through it when a workgroup stages it.
+__host__ __device__ inline int t16_colmap(int ct, int m) {
+  const int g = m >> 2, e = m & 3;
+  return 64 * g + 32 * (ct >> 3) + 31 - (4 * (ct & 7) + e);
+}
 inline int64_t sig_resident_floats(const SigResident& r) {
   return r.on ? (int64_t)r.kt * 8192 + 3 * 256 + 3 * 4 + 256 * 3 : 0;
 }
@@ -372,6 +380,21 @@ template <bool RAW_ROOT>
 __device__ __forceinline__ float window_mid(float m2, float tau_b) {
   const float wb = window_root<RAW_ROOT>(m2) * tau_b * 1.001f;
   return wb < __builtin_inff() ? wb : 0.f;
+}
+
+// Transposed accumulators (D = P X^T: a lane holds columns of ONE row, sig16_kernel and sig16r_kernel alike).
+// The lane's screen: the loosest window any column of the block can have for ITS row - min |y| of a word above it and the exact
+// test is skipped.  A non-finite window (NaN / Inf in the row, a magnitude outside the guarded range): +inf, everything goes to
+// the exact test; a zero row: -1, nothing does.  (const float&: see above)
+__device__ __forceinline__ float row_screen(const float& window, const float& wb, const float& amax_cb, const float& bmax_cb) {
+  const float ts = window < __builtin_inff() ? window * amax_cb + wb * bmax_cb : __builtin_inff();
+  return ts > 0.f ? ts : -1.f;
+}
+// A value's sign into the lane's word of its row's sign string: ONE v_alignbit, the first value shifted in ends highest
+// (res_colmap / t16_colmap order the image by that).  The string holds y < 0 and the key wants y > 0: the word is inverted on its
+// way out - exact zeros are flagged (stage 2 sets their bit), or the whole row is zero (the caller clears the word).
+__device__ __forceinline__ uint32_t shift_sign_in(uint32_t word, const float& y) {
+  return __builtin_amdgcn_alignbit(word, __float_as_uint(y), 31u);
 }
 
 // A list entry: (row << kEntryColBits) | padded key column (sig_shape_ok bounds the columns)

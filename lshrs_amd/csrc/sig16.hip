@@ -47,12 +47,12 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
   constexpr int kIssueStep = kE / kIssues;
   static_assert((kPP + kXPS) % 2 == 0 && kE % kIssues == 0, "DMA issue slots");
   static_assert(3 * kS1ListCap <= kRingFloats, "the epilogue's list stage reuses the ring");
-  // the epilogue's tables: behind the list stage in the ring; the rows' two windows and the list counters behind the ring where
-  // one workgroup owns the CU, inside it (behind the sign words) where two share it: 80 KiB each, to the byte
+  // the epilogue's tables: behind the list stage in the ring; the list counters behind the ring where one workgroup owns the
+  // CU, inside it (behind the sign words) where two share it: 80 KiB each, to the byte
   constexpr int kTabOff = 3 * kS1ListCap;
-  constexpr int kWndOff = W == 8 ? kRingFloats : kTabOff + 768 + kRows * 8;
-  static_assert(kWndOff + 2 * kRows + 4 <= (W == 8 ? kRingFloats + 512 + 4 : kRingFloats), "windows and counters");
-  __shared__ __attribute__((aligned(16))) float lds[W == 8 ? kRingFloats + 512 + 4 : kRingFloats];
+  constexpr int kCntOff = W == 8 ? kRingFloats : kTabOff + 768 + kRows * 8;
+  static_assert(kCntOff + 4 <= (W == 8 ? kRingFloats + 4 : kRingFloats), "list counters");
+  __shared__ __attribute__((aligned(16))) float lds[W == 8 ? kRingFloats + 4 : kRingFloats];
   struct Bf16Pairs { bf16x2 p[4]; };
 
   const int tid = threadIdx.x;
@@ -246,17 +246,20 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
     const int term = k / (2 * RT), j = (k / RT) % 2, rt = k % RT;
     const bf16x8 a = __builtin_bit_cast(bf16x8, term == 2 ? mid[rt] : hi[rt]);
     const bf16x8 b = __builtin_bit_cast(bf16x8, f[j][term == 1 ? 1 : 0]);
+    // D = P X^T (the fragments are the instruction's first operand, x its second - both operands have the same register layout):
+    // lane (r16, g) ends with columns 16 ct + 4 g + e of ITS row r16, as in sig16r_kernel - the epilogue needs one row's window per
+    // lane and one v_alignbit per sign.  The products and their order of accumulation are what they were.
     // Inline asm pins the accumulator to AGPRs and to in-place accumulation: left to the builtin, hipcc renames
     // accumulator tiles between MFMAs (vDst != SrcC) and parks some in VGPRs, i.e. hundreds of v_accvgpr moves and
     // s_nops per loop body.  Dependent MFMAs are four instructions (64 cycles) apart, beyond the 4-pass hazard window.
 #ifdef LSHRS_T16_BUILTIN
-    acc[rt][ct0 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[rt][ct0 + j], 0, 0, 0);
+    acc[rt][ct0 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, acc[rt][ct0 + j], 0, 0, 0);
 #else
     // drain (behind the last barrier, where the two ends of the tile loop join): the wait states are PART of the statement -
     // hipcc may move accumulator tiles between registers at the join, and as two statements it put those moves between
     // the MFMA and its wait states (round 6, odd k-tile counts: the live audit fired; tools/check_mfma_hazards.py looks for it)
-    if (drain) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0\n\ts_nop 7\n\ts_nop 4" : "+a"(acc[rt][ct0 + j]) : "v"(a), "v"(b));
-    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[rt][ct0 + j]) : "v"(a), "v"(b));
+    if (drain) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %2, %1, %0\n\ts_nop 7\n\ts_nop 4" : "+a"(acc[rt][ct0 + j]) : "v"(a), "v"(b));
+    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %2, %1, %0" : "+a"(acc[rt][ct0 + j]) : "v"(a), "v"(b));
 #endif
   };
 
@@ -367,14 +370,17 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
     tile(t, false, hs1, ms1, hs0, ms0);
     tile(t + 1, false, hs0, ms0, hs1, ms1);
   }
+  Bf16Pairs hd[RT], md[RT];                                              // the last tile's set: ONE drain behind the join
   if (t < ktiles) {                                                      // even number of k-tiles: one more, then drain with its set
     tile(t, false, hs1, ms1, hs0, ms0);
 #pragma unroll
-    for (int k = 0; k < kE; ++k) mfma_one(14, k, fb, hs1, ms1, true);
+    for (int rt = 0; rt < RT; ++rt) { hd[rt] = hs1[rt]; md[rt] = ms1[rt]; }
   } else {
 #pragma unroll
-    for (int k = 0; k < kE; ++k) mfma_one(14, k, fb, hs0, ms0, true);
+    for (int rt = 0; rt < RT; ++rt) { hd[rt] = hs0[rt]; md[rt] = ms0[rt]; }
   }
+#pragma unroll
+  for (int k = 0; k < kE; ++k) mfma_one(14, k, fb, hd, md, true);
   // (the wait states after every MFMA of the drain: where the two branches join hipcc may copy accumulator tiles, and
   //  it does not know that the asm in front of such a copy is an MFMA whose result takes passes to arrive)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped prefetches past the last stage must land before exit
@@ -405,155 +411,151 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
   asm volatile("" : "+v"(r16e), "+v"(ge), "+v"(lanee));
   int64_t* l_list = reinterpret_cast<int64_t*>(lds);
   float* l_y = lds + 2 * kS1ListCap;
-  int* l_count = reinterpret_cast<int*>(lds + kWndOff + 2 * kRows);   // [0] staged + overflowed entries, [1] global base
+  int* l_count = reinterpret_cast<int*>(lds + kCntOff);   // [0] staged + overflowed entries, [1] global base
   if (tid == 0) l_count[0] = 0;
 
-  // ---- row statistics -> the two factors of the stage-1 window per row ------------------------------------------------
-  // (window_hi: a row outside the guarded range gets +inf - NOT(|y| > +inf) holds for every y: all of its projections are
-  // re-evaluated.  A true zero row gives y = 0 in both passes.)
-  float* wnd_lds = lds + kWndOff + wave * kWaveRows;
-  float* wnb_lds = lds + kWndOff + kRows + wave * kWaveRows;
-  // the window coefficients of this column block, staged once (behind the list stage, which owns the first 3 x kS1ListCap
-  // floats of the ring): with the proven window the exact test below runs on a third of the 32-column words, and a
-  // global load in front of each of its compares is latency two waves per SIMD cannot hide
+  // ---- the block's tables, staged once behind the list stage (which owns the first 3 x kS1ListCap floats of the ring) ----
+  // The window coefficients: with the proven window the exact test below runs on a third of the 32-column words, and a global
+  // load in front of each of its compares is latency two waves per SIMD cannot hide.  In IMAGE order (t16_colmap: position
+  // 16 ct + m holds the block's column the map names), so a lane reads the coefficients of its four columns of a column tile as
+  // one 16-byte word.
   float* coef_lds = lds + kTabOff;
   static_assert(kTabOff + 512 <= kRingFloats, "coefficients behind the list stage");
 #pragma unroll
-  for (int i = tid; i < 512; i += 64 * W) coef_lds[i] = i < 256 ? args.wa[cb * 256 + i] : args.wb[cb * 256 + i - 256];
-  // compact column blocks (sig_compact): the padded id of every column of this block, and room for the block's sign words
+  for (int i = tid; i < 512; i += 64 * W) {
+    const int src = cb * 256 + t16_colmap((i & 255) >> 4, i & 15);
+    coef_lds[i] = i < 256 ? args.wa[src] : args.wb[src];
+  }
+  // compact column blocks (sig_compact): the padded id of every column of this block, in image order too, and room for the
+  // block's sign words.  Padded blocks: which bits of the block's sign string are key columns (a band's padding columns and the
+  // block's tail have no hyperplane - norm 0, y = +0 - and their key bits are 0)
   int* padcol_lds = reinterpret_cast<int*>(lds + kTabOff + 512);
+  uint32_t* live_lds = reinterpret_cast<uint32_t*>(lds + kTabOff + 512);
   uint32_t* cw_lds = reinterpret_cast<uint32_t*>(lds + kTabOff + 768);
   static_assert(kTabOff + 768 + kRows * 8 <= kRingFloats, "compact tables behind the coefficients");
-  if (COMPACT && tid < 256) padcol_lds[tid] = args.padcol[cb * 256 + tid];
+  if (tid < 256) {                                     // (whole waves: the first four)
+    if (COMPACT) {
+      padcol_lds[tid] = args.padcol[cb * 256 + t16_colmap(tid >> 4, tid & 15)];
+    } else {
+      const unsigned long long live = __builtin_amdgcn_ballot_w64(args.norms[cb * 256 + tid] > 0.f);
+      if (lane == 0) *reinterpret_cast<u32x2*>(live_lds + 2 * wave) = u32x2{(uint32_t)live, (uint32_t)(live >> 32)};
+    }
+  }
+
+  // ---- row statistics -> the two factors of the stage-1 window and the screen, per lane for ITS row (in registers) ------
+  // (window_hi: a row outside the guarded range gets +inf - NOT(|y| > +inf) holds for every y: all of its projections are
+  // re-evaluated.  A true zero row gives y = 0 in both passes.)
+  const float amax_cb = args.wamax[cb], bmax_cb = args.wbmax[cb];
+  float wnd[RT], wnb[RT], tsmax[RT];
+  bool zrow[RT];
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     const float s2 = row_lanes_sum(ss[rt]), m2 = row_lanes_sum(sm[rt]), am = row_lanes_max(amax[rt]);
     const int64_t myrow = row0 + 16 * rt + r16e;
-    if (ge == 0) {
-      wnd_lds[16 * rt + r16e] = window_hi<false>(s2, am, args.tau);
-      wnb_lds[16 * rt + r16e] = window_mid<false>(m2, args.tau_b);
-      if (cb == 0 && args.row_flags != nullptr && myrow < args.n) args.row_flags[myrow] = row_flag_byte(am, s2);
-    }
+    wnd[rt] = window_hi<false>(s2, am, args.tau);
+    wnb[rt] = window_mid<false>(m2, args.tau_b);
+    tsmax[rt] = row_screen(wnd[rt], wnb[rt], amax_cb, bmax_cb);
+    zrow[rt] = am == 0.f;                  // every projection of the row is +0: all bits 0 (a NaN row is flagged wholesale)
+    if (ge == 0 && cb == 0 && args.row_flags != nullptr && myrow < args.n) args.row_flags[myrow] = row_flag_byte(am, s2);
   }
   __builtin_amdgcn_s_waitcnt(0xC07F);
   __builtin_amdgcn_s_barrier();
 
-  // ---- sign bits.  One v_cmp per accumulator register = 4 rows (g') x 16 columns: its low 32 bits are rows g' = 0, 1,
-  // its high 32 bits rows g' = 2, 3 of the tile.  Lane L owns the ROW PAIR p = L / 4 = (rtl, g'-pair, reg) - rows
-  // 16 rtl + 8 g'pair + reg and + 4 - and the 32-column words 2 (L % 4), + 1: the ballot halves of the even column
-  // tile land in A[], of the odd one in B[] (deposit_positive: v_cmp, the two wait states a VALU-written SGPR needs,
-  // two v_writelane), and two VALU ops per word merge the 16-bit halves.
-  const float amax_cb = args.wamax[cb], bmax_cb = args.wbmax[cb];
-  {
-    uint32_t A[2] = {0u, 0u}, B[2] = {0u, 0u};
+  // ---- sign bits, window test, list.  A lane's 64 values of a row are 64 consecutive bits of the row's sign string (the
+  // image is packed in that order): shift_sign_in per value, words 2 g and 2 g + 1 of the block's eight per row.
 #pragma unroll
-    for (int rt = 0; rt < 2; ++rt) {
-      const f32x4 wnd = *reinterpret_cast<const f32x4*>(wnd_lds + 16 * rt + 4 * ge);   // rows 16 rt + 4 g + 0..3
-      const f32x4 wnb = *reinterpret_cast<const f32x4*>(wnb_lds + 16 * rt + 4 * ge);
-      // per-lane screen: the largest window of this lane's four rows (a non-finite window - NaN or Inf in the row, or
-      // a magnitude outside the guarded range - makes it +inf: everything goes to the exact test)
-      float tsmax = __builtin_fmaxf(__builtin_fmaxf(wnd[0], wnd[1]), __builtin_fmaxf(wnd[2], wnd[3]));
-      if (!(wnd[0] < __builtin_inff()) || !(wnd[1] < __builtin_inff()) || !(wnd[2] < __builtin_inff()) ||
-          !(wnd[3] < __builtin_inff()))
-        tsmax = __builtin_inff();
-      tsmax = tsmax * amax_cb +
-              __builtin_fmaxf(__builtin_fmaxf(wnb[0], wnb[1]), __builtin_fmaxf(wnb[2], wnb[3])) * bmax_cb;
-      tsmax = tsmax > 0.f ? tsmax : -1.f;               // all four rows zero: nothing to re-evaluate
+  for (int rt = 0; rt < RT; ++rt) {
+    const int64_t grow = row0 + 16 * rt + r16e;
+    uint32_t word[2] = {0u, 0u};
 #pragma unroll
-      for (int w = 0; w < 8; ++w) {
-        float m = __builtin_inff();                     // min |y| over the 2 tiles x 4 registers of this word (NaN dropped:
-                                                        // a NaN y only comes from a row whose window is non-finite)
+    for (int w = 0; w < 8; ++w) {
+      float m = __builtin_inff();                     // min |y| over the 2 tiles x 4 registers of this word (NaN dropped:
+                                                      // a NaN y only comes from a row whose window is non-finite)
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const float y0 = acc[rt][2 * w][reg], y1 = acc[rt][2 * w + 1][reg];
-          const int p0 = 8 * rt + reg * 2;              // pair (rt, reg, g'pair = 0); g'pair = 1 is p0 + 1
-#ifdef LSHRS_AB_CHEAP_SIGNS      // (A/B builds only: what the transposition through SGPRs costs - one v_alignbit per value instead; wrong keys by design)
-          A[w & 1] = __builtin_amdgcn_alignbit(A[w & 1], __float_as_uint(y0), 31u);
-          B[w & 1] = __builtin_amdgcn_alignbit(B[w & 1], __float_as_uint(y1), 31u);
-#else
-          deposit_positive(A[w & 1], y0, 4 * p0 + (w >> 1), 4 * (p0 + 1) + (w >> 1));
-          deposit_positive(B[w & 1], y1, 4 * p0 + (w >> 1), 4 * (p0 + 1) + (w >> 1));
-#endif
+      for (int half = 0; half < 2; ++half)
+#pragma unroll
+        for (int reg = 0; reg < 4; reg += 2) {
+          const float y0 = acc[rt][2 * w + half][reg], y1 = acc[rt][2 * w + half][reg + 1];
+          word[w >> 2] = shift_sign_in(word[w >> 2], y0);
+          word[w >> 2] = shift_sign_in(word[w >> 2], y1);
           asm("v_min3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(y0), "v"(y1));
         }
-        const bool aud = au_rw == 8 * rt + w;                   // (wave-uniform: this word holds the wave's audit sample)
-        if (__builtin_amdgcn_ballot_w64(!(m > tsmax)) != 0 || aud) {   // wave-uniform: the exact per-element test
-          // With the proven window this runs on a quarter of the words: first the eight comparisons, branch-free, into a
-          // mask; only the lane that holds a flagged projection (one, seldom two of the wave) enters the append.
-          unsigned hits = 0u;
-          float ys[8], thrs[8];
+      const bool aud = au_rw == 8 * rt + w;                   // (wave-uniform: this word holds the wave's audit sample)
+      if (__builtin_amdgcn_ballot_w64(!(m > tsmax[rt])) != 0 || aud) {   // wave-uniform: the exact per-element test
+        // With the proven window this runs on a fraction of the words: first the eight comparisons, branch-free, into a
+        // mask; only the lane that holds a flagged projection (one, seldom two of the wave) enters the append.
+        unsigned hits = 0u;
+        float ys[8], thrs[8];
 #pragma unroll
-          for (int half = 0; half < 2; ++half) {
-            const int ct = 2 * w + half;
-            const float pa = coef_lds[16 * ct + r16e], pb = coef_lds[256 + 16 * ct + r16e];
+        for (int half = 0; half < 2; ++half) {
+          const int ct = 2 * w + half;
+          const f32x4 pa = *reinterpret_cast<const f32x4*>(coef_lds + 16 * ct + 4 * ge);
+          const f32x4 pb = *reinterpret_cast<const f32x4*>(coef_lds + 256 + 16 * ct + 4 * ge);
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-              float thr = wnd[reg] * pa + wnb[reg] * pb;
-              thr = thr > 0.f ? thr : -1.f;                               // zero row / zero-padded column: y is exactly 0
-              ys[4 * half + reg] = acc[rt][ct][reg];
-              thrs[4 * half + reg] = thr;
-              hits |= (!(__builtin_fabsf(ys[4 * half + reg]) > thr) ? 1u : 0u) << (4 * half + reg);
-            }
+          for (int reg = 0; reg < 4; ++reg) {
+            float thr = wnd[rt] * pa[reg] + wnb[rt] * pb[reg];
+            thr = thr > 0.f ? thr : -1.f;                               // zero row / zero-padded column: y is exactly 0
+            ys[4 * half + reg] = acc[rt][ct][reg];
+            thrs[4 * half + reg] = thr;
+            hits |= (!(__builtin_fabsf(ys[4 * half + reg]) > thr) ? 1u : 0u) << (4 * half + reg);
           }
-          if (aud && lanee == au_lane) {
-            // the sample: value au_q of this lane - left for stage 2 with the window it has just been compared with, unless
-            // it is flagged anyway (then stage 2 decides it), sits in a padding column or past the last row
-            float yq = ys[0], tq = thrs[0];
+        }
+        if (aud && lanee == au_lane) {
+          // the sample: value au_q of this lane - left for stage 2 with the window it has just been compared with, unless
+          // it is flagged anyway (then stage 2 decides it), sits in a padding column or past the last row
+          float yq = ys[0], tq = thrs[0];
 #pragma unroll
-            for (int q = 1; q < 8; ++q) {
-              yq = au_q == q ? ys[q] : yq;
-              tq = au_q == q ? thrs[q] : tq;
+          for (int q = 1; q < 8; ++q) {
+            yq = au_q == q ? ys[q] : yq;
+            tq = au_q == q ? thrs[q] : tq;
+          }
+          const int ct = 2 * w + (au_q >> 2), mpos = 4 * ge + (au_q & 3);
+          const int colid = COMPACT ? padcol_lds[16 * ct + mpos] : cb * 256 + t16_colmap(ct, mpos);
+          const bool keep = ((hits >> au_q) & 1u) == 0u && grow < args.n && colid >= 0 && colid < args.row_bytes * 8 &&
+                            tq < __builtin_inff();
+          if (args.col_cap > 0) {           // buckets: the sample rides in its column's segment, marked
+            if (keep) {
+              const int slot = atomicAdd(args.col_count + colid, 1);
+              if (slot < args.col_cap) {
+                const size_t at = (size_t)colid * args.col_cap + slot;
+                args.tie_list[at] = flag_entry(grow, colid) | kAuditBit;
+                args.flag_y[at] = yq;
+                args.flag_thr[at] = tq;
+              }
             }
-            const int64_t grow = row0 + 16 * rt + 4 * ge + (au_q & 3);
-            const int ct = 2 * w + (au_q >> 2);
-            const int colid = COMPACT ? padcol_lds[16 * ct + r16e] : cb * 256 + 16 * ct + r16e;
-            const bool keep = ((hits >> au_q) & 1u) == 0u && grow < args.n && colid >= 0 && colid < args.row_bytes * 8 &&
-                              tq < __builtin_inff();
-            if (args.col_cap > 0) {           // buckets: the sample rides in its column's segment, marked
-              if (keep) {
+          } else {
+            args.audit_list[au_slot] = keep ? flag_entry(grow, colid) : (int64_t)-1;
+            args.audit_vals[2 * au_slot] = yq;
+            args.audit_vals[2 * au_slot + 1] = tq;
+          }
+        }
+        if (hits != 0u) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const int reg = q & 3, ct = 2 * w + (q >> 2);
+            const int colid = COMPACT ? padcol_lds[16 * ct + 4 * ge + reg] : cb * 256 + t16_colmap(ct, 4 * ge + reg);
+            // (a NaN / Inf row also "flags" the zero-padded columns behind the last key column: the plain list carries
+            //  them to stage 2, which skips them; a bucket launch has no segment for them)
+            if (((hits >> q) & 1u) != 0u && grow < args.n && (!COMPACT || colid >= 0) &&
+                (args.col_cap == 0 || colid < args.row_bytes * 8)) {
+              const int64_t entry = flag_entry(grow, colid);
+              const float yk = ykeep(wnd[rt], ys[q]);
+              const int pos = atomicAdd(l_count, 1);                    // LDS atomic
+              if (pos < kS1ListCap) {
+                l_list[pos] = entry;
+                l_y[pos] = yk;
+              } else if (args.col_cap > 0) {                            // LDS stage full, buckets: straight to the column's segment
+                atomicAdd(args.tie_count, 1);
                 const int slot = atomicAdd(args.col_count + colid, 1);
                 if (slot < args.col_cap) {
-                  const size_t at = (size_t)colid * args.col_cap + slot;
-                  args.tie_list[at] = flag_entry(grow, colid) | kAuditBit;
-                  args.flag_y[at] = yq;
-                  args.flag_thr[at] = tq;
+                  args.tie_list[(size_t)colid * args.col_cap + slot] = entry;
+                  args.flag_y[(size_t)colid * args.col_cap + slot] = yk;
                 }
-              }
-            } else {
-              args.audit_list[au_slot] = keep ? flag_entry(grow, colid) : (int64_t)-1;
-              args.audit_vals[2 * au_slot] = yq;
-              args.audit_vals[2 * au_slot + 1] = tq;
-            }
-          }
-          if (hits != 0u) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-              const int reg = q & 3, ct = 2 * w + (q >> 2);
-              const int64_t grow = row0 + 16 * rt + 4 * ge + reg;
-              const int colid = COMPACT ? padcol_lds[16 * ct + r16e] : cb * 256 + 16 * ct + r16e;
-              // (a NaN / Inf row also "flags" the zero-padded columns behind the last key column: the plain list carries
-              //  them to stage 2, which skips them; a bucket launch has no segment for them)
-              if (((hits >> q) & 1u) != 0u && grow < args.n && (!COMPACT || colid >= 0) &&
-                  (args.col_cap == 0 || colid < args.row_bytes * 8)) {
-                const int64_t entry = flag_entry(grow, colid);
-                const float yk = ykeep(wnd[reg], ys[q]);
-                const int pos = atomicAdd(l_count, 1);                    // LDS atomic
-                if (pos < kS1ListCap) {
-                  l_list[pos] = entry;
-                  l_y[pos] = yk;
-                } else if (args.col_cap > 0) {                            // LDS stage full, buckets: straight to the column's segment
-                  atomicAdd(args.tie_count, 1);
-                  const int slot = atomicAdd(args.col_count + colid, 1);
-                  if (slot < args.col_cap) {
-                    args.tie_list[(size_t)colid * args.col_cap + slot] = entry;
-                    args.flag_y[(size_t)colid * args.col_cap + slot] = yk;
-                  }
-                } else {                                                  // LDS stage full (rows flagged wholesale): straight out
-                  const int slot = atomicAdd(args.tie_count, 1);
-                  if (slot < args.tie_cap) {
-                    args.tie_list[slot] = entry;
-                    if (args.flag_y != nullptr) args.flag_y[slot] = yk;
-                  }
+              } else {                                                  // LDS stage full (rows flagged wholesale): straight out
+                const int slot = atomicAdd(args.tie_count, 1);
+                if (slot < args.tie_cap) {
+                  args.tie_list[slot] = entry;
+                  if (args.flag_y != nullptr) args.flag_y[slot] = yk;
                 }
               }
             }
@@ -561,22 +563,17 @@ __global__ __launch_bounds__(64 * W, 8 / W) void sig16_kernel(const SigArgs args
         }
       }
     }
-    // lane L: pair p = L / 4 -> rows lo / lo + 4, words 2 (L % 4), + 1
-    const int pr = lanee >> 2, wq = 2 * (lanee & 3);
-    const int rlo = 16 * (pr >> 3) + 8 * (pr & 1) + ((pr >> 1) & 3);
-    const uint32_t wlo[2] = {(A[0] & 0xFFFFu) | (B[0] << 16), (A[1] & 0xFFFFu) | (B[1] << 16)};
-    const uint32_t whi[2] = {(A[0] >> 16) | (B[0] & 0xFFFF0000u), (A[1] >> 16) | (B[1] & 0xFFFF0000u)};
-    const int byte0 = (cb * 8 + wq) * 4;
-#pragma unroll
-    for (int hl = 0; hl < 2; ++hl) {
-      const int64_t grow = row0 + rlo + 4 * hl;
-      if (COMPACT) {                  // the block's sign string of this row: to LDS, the key bytes are cut from it below
-        uint32_t* dstw = cw_lds + (wave * kWaveRows + rlo + 4 * hl) * 8 + wq;
-        dstw[0] = hl ? whi[0] : wlo[0];
-        dstw[1] = hl ? whi[1] : wlo[1];
-      } else if (grow < args.n) {
+    // the lane's 64 bits of row 16 rt + r16: words 2 g, 2 g + 1 of the block's part of the row's sign string
+    uint32_t w0 = zrow[rt] ? 0u : ~word[0], w1 = zrow[rt] ? 0u : ~word[1];
+    const int byte0 = (cb * 8 + 2 * ge) * 4;
+    if (COMPACT) {                  // the block's sign string of this row: to LDS, the key bytes are cut from it below
+      *reinterpret_cast<u32x2*>(cw_lds + (wave * kWaveRows + 16 * rt + r16e) * 8 + 2 * ge) = u32x2{w0, w1};
+    } else {
+      const u32x2 live = *reinterpret_cast<const u32x2*>(live_lds + 2 * ge);
+      w0 &= live[0];
+      w1 &= live[1];
+      if (grow < args.n) {
         uint8_t* dst = args.keys + grow * (int64_t)args.row_bytes + byte0;
-        const uint32_t w0 = hl ? whi[0] : wlo[0], w1 = hl ? whi[1] : wlo[1];
         if (args.vec_store && byte0 + 8 <= args.row_bytes) {
           *reinterpret_cast<u32x2*>(dst) = u32x2{w0, w1};
         } else {
@@ -648,9 +645,6 @@ uint32_t lshrs_flags_sig16(void) {
 #endif
 #ifdef LSHRS_AB_NO_STATIC_PRIO
   f |= LSHRS_BUILD_TUNED | (1u << 16);
-#endif
-#ifdef LSHRS_AB_CHEAP_SIGNS
-  f |= LSHRS_BUILD_WRONG_KEYS | (1u << 22);
 #endif
 #ifdef LSHRS_T16_BUILTIN
   f |= LSHRS_BUILD_TUNED | (1u << 20);

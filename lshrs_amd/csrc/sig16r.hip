@@ -236,8 +236,7 @@ __global__ __launch_bounds__(64 * res_waves(NCT, KT), 1) void sig16r_kernel(cons
       if (g == 0 && args.row_flags != nullptr && myrow < args.n) args.row_flags[myrow] = row_flag_byte(am, s2);
       wnd[rt] = window;
       wnb[rt] = wb_;
-      float ts = window < __builtin_inff() ? window * amax_cb + wb_ * bmax_cb : __builtin_inff();
-      tsmax[rt] = ts > 0.f ? ts : -1.f;                  // a zero row: nothing to re-evaluate
+      tsmax[rt] = row_screen(window, wb_, amax_cb, bmax_cb);
       zrow[rt] = am == 0.f;                              // every projection of the row is +0: all bits 0 (a NaN row is flagged wholesale)
     }
 
@@ -253,8 +252,7 @@ __global__ __launch_bounds__(64 * res_waves(NCT, KT), 1) void sig16r_kernel(cons
 
     // ---- sign bits, window test, list ------------------------------------------------------------------------------
     // A lane's 4 NCT values of a row are 4 NCT consecutive bits of the row's sign string (res_colmap: the image is packed in
-    // that order): ONE v_alignbit per value shifts the accumulator's sign into the lane's word - the string holds y < 0, the
-    // key wants y > 0: the word is inverted on its way out (exact zeros are flagged, or the whole row is zero).
+    // that order): shift_sign_in per value; the word is inverted on its way out.
     {
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
@@ -265,15 +263,15 @@ __global__ __launch_bounds__(64 * res_waves(NCT, KT), 1) void sig16r_kernel(cons
 #pragma unroll
           for (int reg = 0; reg < 4; reg += 2) {
             const float y0 = acc[rt][2 * w][reg], y1 = acc[rt][2 * w][reg + 1];
-            word[w >> 2] = __builtin_amdgcn_alignbit(word[w >> 2], __float_as_uint(y0), 31u);
-            word[w >> 2] = __builtin_amdgcn_alignbit(word[w >> 2], __float_as_uint(y1), 31u);
+            word[w >> 2] = shift_sign_in(word[w >> 2], y0);
+            word[w >> 2] = shift_sign_in(word[w >> 2], y1);
             asm("v_min3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(y0), "v"(y1));        // (NaN dropped)
           }
 #pragma unroll
           for (int reg = 0; reg < 4; reg += 2) {
             const float y0 = acc[rt][2 * w + 1][reg], y1 = acc[rt][2 * w + 1][reg + 1];
-            word[w >> 2] = __builtin_amdgcn_alignbit(word[w >> 2], __float_as_uint(y0), 31u);
-            word[w >> 2] = __builtin_amdgcn_alignbit(word[w >> 2], __float_as_uint(y1), 31u);
+            word[w >> 2] = shift_sign_in(word[w >> 2], y0);
+            word[w >> 2] = shift_sign_in(word[w >> 2], y1);
             asm("v_min3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(y0), "v"(y1));
           }
           const bool aud = au_rw == 8 * rt + w;

@@ -135,9 +135,9 @@ __global__ void compact_gather_kernel(const float* __restrict__ src, const int* 
 //           4 registers; workgroup = 4 waves, one per SIMD, 256 rows; grid = ceil(n / 256) x column blocks.
 //   stage = (k-tile t of 32, column half ch): 16 KiB of fragments = 8 column tiles x {hi, mid}, 96 MFMAs per
 //           wave (16 cycles each) in two quarters of 48; x is read back and split once per k-tile.
-//   image = image16[cb][t][ct 0..15][part][lane]: 16 bytes = the 8 bf16 of P'[col = 256 cb + 16 ct + (lane & 15)]
+//   image = image16[cb][t][ct 0..15][part][lane]: 16 bytes = the 8 bf16 of P'[col = 256 cb + t16_colmap(ct, lane & 15)]
 //           [k = 32 t + 8 (lane >> 4) + 0..7]: a stage is 16 KiB contiguous, staged by a linear LDS-DMA copy.
-//   accumulator tile: column = lane & 15, row = 4 (lane >> 4) + register.
+//   accumulator tile (D = P X^T): row = lane & 15, column position m = 4 (lane >> 4) + register of the column tile.
 // ------------------------------------------------------------------------------------------
 __global__ void pack_image_bf16_t16_kernel(const float* __restrict__ P, int num_bands, int rows, int dim, int bb,
                                            int ktiles, int64_t chunks, u16x8* __restrict__ image, int bpb = 0, int res_nct = 0) {
@@ -149,7 +149,8 @@ __global__ void pack_image_bf16_t16_kernel(const float* __restrict__ P, int num_
   const int64_t t = c >> 11;
   const int kt = (int)(t % ktiles);
   const int cb = (int)(t / ktiles);
-  const int col = cb * 256 + ct * 16 + (lane & 15);
+  // (the column at this position of its block: sig16_kernel's order, t16_colmap - a lane's values are consecutive bits of its row's sign string)
+  const int col = cb * 256 + t16_colmap(ct, lane & 15);
   int band = col / (bb * 8);
   int bit = col % (bb * 8);
   if (bpb > 0) {                                     // compact column blocks: bpb whole bands per block, no padding inside
