@@ -694,6 +694,37 @@ int lshrs_scan_above_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32
                          const float* queries, int32_t q, const float* bars, int64_t capacity, int32_t* out_query,
                          int64_t* out_row, float* out_approx, uint64_t* total, void* workspace, int32_t* err, void* stream);
 
+/* ---- self-join (csrc/scan.hip; lshrs_amd.exact_pairs_above): every PAIR of live rows of corpus whose APPROXIMATE cosine
+ * reaches `bar` - the range scan with the stored rows themselves as the queries.  A pair is emitted once, as (a, b) with
+ * a < b by row position: out_a / out_b int64 (the rows), out_approx float; no row against itself.  The approximate score is
+ * the one lshrs_scan_above_* gives row b for row a converted to f32 as the query, bit for bit (a one-term row - bf16, int8,
+ * e4m3fn - is exact in bf16: the query's second term is zero and is neither stored nor multiplied), so lshrs_scan_epsilon
+ * bounds it unchanged.  The rows are taken as queries a block at a time, one launch per block on `stream`, all through one
+ * cursor: qblock = 0 takes the planned block (at most 8192 rows, fewer where the image would pass 256 MiB), another multiple
+ * of 64 is taken as the block.  capacity, the three arrays, total (zeroed by the entry on the stream; counts the pairs beyond
+ * capacity too), row_ids, err, the limits of dim and m and the status codes: as for lshrs_scan_above_*; err bit 4: a live row
+ * of zero norm as a query, bit 1: as a row.  A dead row is in no pair and sets no bit.  Live entries of row_ids are taken to
+ * be distinct (not checked).  qblock negative or no multiple of 64: LSHRS_E_BADARG; more than 65535 tiles of 64 in a block:
+ * LSHRS_E_TOOLARGE.  workspace: lshrs_scan_pairs_workspace_bytes(m, dim, qblock) bytes at a 16-byte aligned address: the
+ * image of one block (16 KiB per tile of 64 rows and chunk of 64 elements; the one-term types use half), a norm per row of
+ * the block, and 16.  No host synchronisation.  (Additive to ABI 7.) */
+int64_t lshrs_scan_pairs_workspace_bytes(int64_t m, int32_t dim, int32_t qblock);
+int lshrs_scan_pairs_f32(const float* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
+                          int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
+                          void* workspace, int32_t* err, void* stream);
+int lshrs_scan_pairs_bf16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
+                          int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
+                          void* workspace, int32_t* err, void* stream);
+int lshrs_scan_pairs_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
+                          int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
+                          void* workspace, int32_t* err, void* stream);
+int lshrs_scan_pairs_i8(const int8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
+                          int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
+                          void* workspace, int32_t* err, void* stream);
+int lshrs_scan_pairs_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
+                          int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
+                          void* workspace, int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,10 @@ The ground truth an approximate index is measured against (``LSHRS.recall``) and
 threshold.  No window, no unsettled query: the first pass lets through whatever reaches ``threshold - (epsilon +
 rerank_rounding)``, which no row of the answer can lie below, and the rerank's kernel decides the rest.
 
+``exact_pairs_above`` is the self-join on that pass (``lshrs_scan_pairs_*``): every pair of live rows whose rerank score reaches
+a threshold - the stored rows are their own queries, every unordered pair is multiplied once, and the rerank's kernel judges what
+the pass lets through, the row of the lower id as the query.
+
 No CPU compute path: the host moves arrays, decides which queries are settled from three numbers per query, and keeps counts.
 """
 
@@ -32,8 +36,8 @@ from . import _native
 from .similarity import (_CORPUS_ENTRY, _CORPUS_ENTRY_8BIT, _on_device, _raise_for_status, corpus_suffix, cosine_ragged_device,
                          cosine_scores_device, topk_desc_device)
 
-__all__ = ["exact_top_k", "exact_above", "settled", "choose_window", "rerank_rounding", "scan_epsilon", "scan_max_window",
-           "scan_windows", "scan_above", "above_bars", "above_recall"]
+__all__ = ["exact_top_k", "exact_above", "exact_pairs_above", "settled", "choose_window", "rerank_rounding", "scan_epsilon",
+           "scan_max_window", "scan_windows", "scan_above", "scan_pairs", "above_bars", "above_recall"]
 
 METHODS = ("auto", "scan", "gather")
 # (query, live row) pairs of one chunk of the gather.  Per pair: 4 B of score, 8 B of candidate row, 1 B of status, and up to
@@ -43,6 +47,10 @@ _SCAN_MAX_DIM = 16384               # what lshrs_scan_topk_* and lshrs_cosine_* 
 _SCAN_MAX_ROWS = (1 << 31) - 1
 # slots of the range search's first launch: max(this, 64 per query) pairs of 16 bytes; more pairs than that cost a second launch
 _ABOVE_FIRST_CAPACITY = 1 << 20
+# ... and of the self-join's: pairs of 20 bytes
+_PAIRS_FIRST_CAPACITY = 1 << 20
+# float32 bytes of the lower-id rows one chunk of the self-join's rescoring gathers as queries
+_PAIRS_QUERY_BYTES = 1 << 28
 
 
 def scan_max_window() -> int:
@@ -175,16 +183,25 @@ def _search_args(queries, corpus, row_ids, caller: str):
             raise ValueError(f"queries must have shape (q, {int(corpus.shape[1])}); received {tuple(d_q.shape)}")
         d_q = d_q.to(device=dev, dtype=torch.float32).contiguous()
         q, m, dim = int(d_q.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
-        if dim > _SCAN_MAX_DIM or m > _SCAN_MAX_ROWS:
-            # (beyond the scan and beyond the rerank's entries alike: what a rerank of such rows raises, before any launch)
-            raise _native.NativeLibraryError(f"{caller}: shape outside kernel limits (LSHRS_E_TOOLARGE): {m} rows of {dim} "
-                                             f"elements; at most {_SCAN_MAX_ROWS} rows of {_SCAN_MAX_DIM}")
-        d_ids = None
-        if row_ids is not None:
-            d_ids = _on_device(torch, row_ids, np.int64).to(device=dev, dtype=torch.int64).contiguous()
-            if d_ids.dim() != 1 or int(d_ids.shape[0]) != m:
-                raise ValueError(f"row_ids must have shape ({m},); received {tuple(d_ids.shape)}")
+        d_ids = _rows_args(torch, corpus, row_ids, caller)
     return d_q, d_ids, q, m, dim
+
+
+def _rows_args(torch, corpus, row_ids, caller: str):
+    """The rows' half of :func:`_search_args` (and all of it for ``exact_pairs_above``, which has no queries): the shape within
+    the kernels' limits, ``row_ids`` as an int64 ``(m,)`` tensor on the corpus's device (or None)."""
+    dev = corpus.device
+    m, dim = int(corpus.shape[0]), int(corpus.shape[1])
+    if dim > _SCAN_MAX_DIM or m > _SCAN_MAX_ROWS:
+        # (beyond the scan and beyond the rerank's entries alike: what a rerank of such rows raises, before any launch)
+        raise _native.NativeLibraryError(f"{caller}: shape outside kernel limits (LSHRS_E_TOOLARGE): {m} rows of {dim} "
+                                         f"elements; at most {_SCAN_MAX_ROWS} rows of {_SCAN_MAX_DIM}")
+    d_ids = None
+    if row_ids is not None:
+        d_ids = _on_device(torch, row_ids, np.int64).to(device=dev, dtype=torch.int64).contiguous()
+        if d_ids.dim() != 1 or int(d_ids.shape[0]) != m:
+            raise ValueError(f"row_ids must have shape ({m},); received {tuple(d_ids.shape)}")
+    return d_ids
 
 
 def _finish(stats: Optional[Dict], out: Dict, tensors, return_tensors: bool):
@@ -412,6 +429,169 @@ def exact_above(queries, corpus, threshold, *, row_ids=None, max_pairs: int = 1 
                 bounds[1:] = torch.cumsum(torch.bincount(pq, minlength=q), 0)
                 out["kept"] = int(ids.shape[0])
     return _finish(stats, out, (ids, scores, bounds), return_tensors)
+
+
+# ------------------------------------------------------------------------------------------
+# self-join: every pair of live rows at or above a cosine threshold
+# ------------------------------------------------------------------------------------------
+def scan_pairs(corpus, bar: float, capacity: int, row_ids=None, qblock: int = 0):
+    """Device-level entry of the self-join's first pass (``lshrs_scan_pairs_*``): ``corpus`` / ``row_ids`` as
+    :func:`scan_windows` takes them, ``bar`` one float32 for every pair, ``qblock`` the rows taken as queries per launch (0: the
+    library's plan; else a multiple of 64).  Returns ``(a (capacity,) int64, b (capacity,) int64, approx (capacity,) float32,
+    total uint64-as-int64[1], err int32[1])``: the first ``min(total, capacity)`` slots are pairs of row POSITIONS, ``a < b``,
+    in no particular order; ``total`` counts every pair that reached the bar."""
+    torch = _native.require_gpu()
+    lib = _native.load()
+    entry = "lshrs_scan_pairs_" + corpus_suffix(corpus)
+    dev = corpus.device
+    m, dim = int(corpus.shape[0]), int(corpus.shape[1])
+    capacity = int(capacity)
+    out_a = torch.empty((capacity,), dtype=torch.int64, device=dev)
+    out_b = torch.empty((capacity,), dtype=torch.int64, device=dev)
+    out_approx = torch.empty((capacity,), dtype=torch.float32, device=dev)
+    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    if m == 0:
+        return out_a, out_b, out_approx, total, err
+    with torch.cuda.device(dev):
+        ws = _scan_workspace(torch, lib, "lshrs_scan_pairs_workspace_bytes", dev, m, dim, int(qblock))
+        _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim,
+                                          row_ids.data_ptr() if row_ids is not None else None, float(bar), int(qblock), capacity,
+                                          out_a.data_ptr() if capacity else None, out_b.data_ptr() if capacity else None,
+                                          out_approx.data_ptr() if capacity else None, total.data_ptr(), ws.data_ptr(),
+                                          err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), entry)
+    return out_a, out_b, out_approx, total, err
+
+
+def _pairs_block(lib, m: int, dim: int) -> int:
+    """The rows ``lshrs_scan_pairs_*`` plans to take as queries per launch, read out of the workspace's size: the image of one
+    block (16 KiB per tile of 64 rows and chunk of 64 elements), 256 bytes of norms per tile, and 16 bytes."""
+    nbytes = int(lib.lshrs_scan_pairs_workspace_bytes(m, dim, 0))
+    if nbytes < 0:
+        _native.check(nbytes, "lshrs_scan_pairs_workspace_bytes")
+    return (nbytes - 16) // (-(-dim // 64) * 16384 + 256) * 64
+
+
+def _rows_as_f32(torch, corpus, rows):
+    """The rows ``rows`` (int64, on the device) of ``corpus`` as a contiguous float32 tensor - each element converted exactly.
+    (8-bit floats are gathered as bytes: indexing is not defined for them everywhere.)"""
+    if corpus.dtype.is_floating_point and corpus.element_size() == 1:
+        return corpus.view(torch.uint8)[rows].view(corpus.dtype).float().contiguous()
+    return corpus[rows].float().contiguous()
+
+
+def _check_pairs_args(threshold, max_pairs) -> float:
+    """The threshold of ``exact_pairs_above`` as a float; ``ValueError`` for what it does not take.  Pure host."""
+    if int(max_pairs) < 0:
+        raise ValueError(f"max_pairs must be >= 0; received {max_pairs}")
+    try:
+        t = np.asarray(threshold, dtype=np.float64)
+    except (TypeError, ValueError) as exc:
+        raise ValueError("threshold must be a number") from exc
+    if t.ndim != 0:
+        raise ValueError(f"threshold must be one number for all pairs; received an array of shape {t.shape}")
+    return float(_check_above_args(1, float(t), max_pairs)[0])
+
+
+def exact_pairs_above(corpus, threshold, *, row_ids=None, max_pairs: int = 1 << 26, return_tensors: bool = False,
+                      stats: Optional[Dict] = None):
+    """Every pair of rows of ``corpus`` at or above a cosine ``threshold``, exactly - the near-duplicates among the stored
+    vectors: ``(ids_a (p,) int64, ids_b (p,) int64, scores (p,) float32)`` with ``ids_a < ids_b`` in every pair, scores
+    descending, equal scores by ascending ``(ids_a, ids_b)``; NumPy arrays, or device tensors with ``return_tensors``.
+
+    ``corpus``, ``row_ids``: as :func:`exact_top_k` takes them (live entries of ``row_ids`` are taken to be distinct).
+    ``threshold``: one number, finite and within [-1, 1], else ``ValueError`` before anything touches the GPU.  The pair
+    ``{a, b}`` of live rows belongs to the answer exactly when its RERANK score reaches ``float32(threshold)``, and the score of
+    a pair is DEFINED with the row of the lower id, converted to float32, as the query and the row of the higher id as the row
+    (``lshrs_cosine_ragged_*``; it is the score returned): the rerank's score is not symmetric in its last bit, and the ids,
+    unlike the rows' positions, are the caller's.  It is the answer :func:`exact_above` ``(corpus.float(), corpus, threshold)``
+    gives, cut to ``query id < row id``.
+
+    One pass over the rows on the matrix cores (``lshrs_scan_pairs_*``) with the rows themselves as the queries, a block of
+    them at a time, multiplies every unordered pair once and emits what reaches :func:`above_bars` ``(threshold, scan_epsilon
+    + rerank_rounding)`` - both bounds are about the true cosine, which is symmetric, so the bar holds for either orientation;
+    the distinct lower-id rows of the emitted pairs are gathered as float32 queries, in chunks of bounded memory, the rerank's
+    kernel scores the pairs, and the cut and the order are made on the device.  Capacity as in :func:`exact_above`: beyond
+    ``2^20`` pairs the pass runs a second time with room for all; beyond ``max_pairs`` the call raises ``ValueError``.
+    ``stats``: a dict that receives ``rows``, ``emitted``, ``kept``, ``launches`` (1 or 2), ``blocks`` (row blocks of a pass)
+    and ``epsilon``.
+
+    A live row of zero norm raises ``ValueError("Cannot normalize zero vector")``; rows beyond the kernels raise the
+    ``NativeLibraryError`` :func:`exact_top_k` raises."""
+    max_pairs = int(max_pairs)
+    t = _check_pairs_args(threshold, max_pairs)
+    torch = _native.require_gpu()
+    lib = _native.load()
+    corpus_suffix(corpus)
+    dev = corpus.device
+    with torch.cuda.device(dev):
+        d_ids = _rows_args(torch, corpus, row_ids, "exact_pairs_above")
+        m, dim = int(corpus.shape[0]), int(corpus.shape[1])
+        eps = scan_epsilon(corpus.dtype, dim)
+        out = {"rows": m, "emitted": 0, "kept": 0, "launches": 0, "blocks": 0, "epsilon": eps}
+        ids_a = torch.empty((0,), dtype=torch.int64, device=dev)
+        ids_b = torch.empty((0,), dtype=torch.int64, device=dev)
+        scores = torch.empty((0,), dtype=torch.float32, device=dev)
+        if m:
+            bar = float(above_bars(np.array([t]), eps + rerank_rounding(dim))[0])
+            t32 = float(np.float32(t))
+            out["blocks"] = -(-m // _pairs_block(lib, m, dim))
+            capacity = min(_PAIRS_FIRST_CAPACITY, max_pairs)
+            pa, pb, _, total, err = scan_pairs(corpus, bar, capacity, d_ids)
+            emitted = int(total.item())                 # (the one size that crosses to the host)
+            out["launches"] = 1
+            if int(err.item()) & 5:
+                raise ValueError("Cannot normalize zero vector")
+            if emitted > max_pairs:
+                raise ValueError(f"exact_pairs_above: {emitted} pairs reach the threshold's bar, more than max_pairs = "
+                                 f"{max_pairs}")
+            if emitted > capacity:
+                del pa, pb
+                pa, pb, _, total, err = scan_pairs(corpus, bar, emitted, d_ids)
+                out["launches"] = 2
+                if int(total.item()) != emitted:        # (the same launches on the same data: the same count)
+                    raise RuntimeError("exact_pairs_above: the second pass counted other pairs than the first")
+            out["emitted"] = emitted
+            if emitted:
+                pa, pb = pa[:emitted], pb[:emitted]
+                # the orientation is by id: the row of the lower id asks, the row of the higher id is scored
+                if d_ids is not None:
+                    ia, ib = d_ids[pa], d_ids[pb]
+                    swap = ia > ib
+                    pa, pb = torch.where(swap, pb, pa), torch.where(swap, pa, pb)
+                    ia, ib = torch.where(swap, ib, ia), torch.where(swap, ia, ib)
+                else:
+                    ia, ib = pa, pb
+                # by asking row (stable): its pairs are one ragged list; the distinct asking rows a chunk at a time as queries
+                pa, by_a = torch.sort(pa, stable=True)
+                pb, ia, ib = pb[by_a].contiguous(), ia[by_a], ib[by_a]
+                urows, count = torch.unique_consecutive(pa, return_counts=True)
+                off = (torch.cumsum(count, 0) - count).contiguous()
+                count32 = count.to(torch.int32)
+                exact = torch.empty((emitted,), dtype=torch.float32, device=dev)
+                err2 = torch.zeros(1, dtype=torch.int32, device=dev)
+                step = max(1, _PAIRS_QUERY_BYTES // (4 * dim))
+                for lo in range(0, int(urows.shape[0]), step):
+                    hi = min(int(urows.shape[0]), lo + step)
+                    queries = _rows_as_f32(torch, corpus, urows[lo:hi])
+                    cosine_ragged_device(corpus, queries, pb, off[lo:hi].contiguous(), count32[lo:hi].contiguous(), emitted,
+                                         scores=exact, err=err2)
+                if int(err2.item()) & 5:
+                    raise ValueError("Cannot normalize zero vector")
+                keep = exact >= t32                     # (a NaN is not kept)
+                ia, ib, exact = ia[keep], ib[keep], exact[keep]
+                # ascending (ids_a, ids_b) by two stable sorts, then ONE stable sort on an integer that descends with the score
+                # (-0.0 with 0.0): descending score, ties in the id order
+                _, order = torch.sort(ib, stable=True)
+                ia, ib, exact = ia[order], ib[order], exact[order]
+                _, order = torch.sort(ia, stable=True)
+                ia, ib, exact = ia[order], ib[order], exact[order]
+                bits = (exact + 0.0).view(torch.int32)
+                down = 0x7FFFFFFF - torch.where(bits >= 0, bits, bits ^ 0x7FFFFFFF).long()     # in [0, 2^32)
+                _, order = torch.sort(down, stable=True)
+                ids_a, ids_b, scores = ia[order].contiguous(), ib[order].contiguous(), exact[order].contiguous()
+                out["kept"] = int(ids_a.shape[0])
+    return _finish(stats, out, (ids_a, ids_b, scores), return_tensors)
 
 
 def above_recall(truth_ids, truth_scores, truth_bounds, cand_ids, cand_bounds, num_bands: int, rows_per_band: int) -> Dict:

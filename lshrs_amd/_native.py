@@ -228,6 +228,12 @@ def _declare(lib: ctypes.CDLL) -> None:
     for dt in SCAN_ELEMS:
         above = getattr(lib, "lshrs_scan_above_" + dt)
         above.argtypes, above.restype = [vp, i64, i64, i32, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp], c.c_int
+    lib.lshrs_scan_pairs_workspace_bytes.argtypes = [i64, i32, i32]
+    lib.lshrs_scan_pairs_workspace_bytes.restype = i64
+    # (corpus, m, ldc, dim, row_ids, bar, qblock, capacity, out_a, out_b, out_approx, total, workspace, err, stream)
+    for dt in SCAN_ELEMS:
+        pairs = getattr(lib, "lshrs_scan_pairs_" + dt)
+        pairs.argtypes, pairs.restype = [vp, i64, i64, i32, vp, f32, i32, i64, vp, vp, vp, vp, vp, vp, vp], c.c_int
     lib.lshrs_pipe_create.argtypes = [i32, i32, i32, i32, i32]
     lib.lshrs_pipe_create.restype = vp
     lib.lshrs_pipe_destroy.argtypes = [vp]
@@ -302,6 +308,12 @@ EXPORTS = (
     "lshrs_scan_above_f16",
     "lshrs_scan_above_i8",
     "lshrs_scan_above_f8e4m3",
+    "lshrs_scan_pairs_workspace_bytes",
+    "lshrs_scan_pairs_f32",
+    "lshrs_scan_pairs_bf16",
+    "lshrs_scan_pairs_f16",
+    "lshrs_scan_pairs_i8",
+    "lshrs_scan_pairs_f8e4m3",
     "lshrs_pipe_create",
     "lshrs_pipe_destroy",
     "lshrs_pipe_hash_f32",

@@ -687,6 +687,22 @@ class LSHRS:
         with _gc_paused():
             return qh.split_rows(list(zip(ids.tolist(), scores.astype(np.float64).tolist())), np.diff(bounds))
 
+    def pairs_exact_above(self, threshold, *, return_arrays: bool = False):
+        """Every pair of indexed vectors at or above a cosine ``threshold`` (one number), EXACTLY - the near-duplicates among
+        what is indexed: the self-join beside :meth:`search_exact_above`, over the same corpus
+        (``lshrs_amd.exact_pairs_above``) and with the same errors where there is none.  Returns ``[(id_a, id_b, score),
+        ...]`` with ``id_a < id_b``, scores descending and equal scores by ascending ``(id_a, id_b)`` - or ``(ids_a, ids_b,
+        scores)`` arrays with ``return_arrays``.  ``last_search_stats`` tells what the call did."""
+        from ._exact import exact_pairs_above
+
+        ids_a, ids_b, scores = self._search_corpus("pairs_exact_above", lambda store, _, t: store.pairs_above(t),
+                                                   lambda _, table, t, stats: exact_pairs_above(table, t, stats=stats), None,
+                                                   threshold)
+        if return_arrays:
+            return ids_a, ids_b, scores
+        with _gc_paused():
+            return list(zip(ids_a.tolist(), ids_b.tolist(), scores.astype(np.float64).tolist()))
+
     def recall_above(self, vectors, threshold) -> Dict[str, Any]:
         """What the index finds of the pairs it is configured for, measured: the truth is :meth:`search_exact_above`
         ``(vectors, threshold)``, the candidates are :meth:`query_many` ``(vectors, top_k=None)`` - every id that shares a

@@ -20,7 +20,11 @@
 // scan_merge_kernel orders the slices' winners of a query in LDS.  No global atomics but the error bits.
 // Range scan (scan_above_kernel, lshrs_scan_above_*): the same first pass with no selection at all - every (query, live row)
 // whose approximate score reaches the query's bar is emitted to flat arrays through one global cursor (lshrs_amd.exact_above).
-// The pass (rows in, dot products and norms out) is written once, in scan_pass.inc, and compiled into both kernels.
+// Self-join (scan_pairs_kernel, lshrs_scan_pairs_*): the range scan with a block of the stored rows themselves as the queries -
+// image and norms built straight from the rows (scan_pairs_prep_kernel, scan_pairs_qnorm_kernel), every unordered pair of live
+// rows multiplied once (a block scans the rows from its own first row on, a workgroup from its tile's; diagonal tiles masked
+// lane by lane), one MFMA per step for the one-term types, whose image holds no mid term (lshrs_amd.exact_pairs_above).
+// The pass (rows in, dot products and norms out) is written once, in scan_pass.inc, and compiled into all three kernels.
 // ABI and reference citations: include/lshrs_hip.h.  Design notes, the epsilon derivation and the roof: DESIGN.md.
 #include "lshrs_common.h"
 
@@ -284,6 +288,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
                                                             uint64_t* __restrict__ parts, int32_t* __restrict__ err) {
   using T = typename ScanElem<E>::T;
   constexpr bool kTwo = ScanElem<E>::kTerms == 2;
+  constexpr int kBTerms = 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char scan_lds[];
   u32x4* bl = reinterpret_cast<u32x4*>(scan_lds);
   uint64_t* items = reinterpret_cast<uint64_t*>(scan_lds + kScanChunkBytes);
@@ -387,8 +392,9 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
 // scan_kernel includes the same text inline instead of calling this: the call moved its register allocation (spills and
 // scratch of seven of its ten instantiations - measured in commit f6cea70, "Exact range search: every stored vector at or above a
 // cosine threshold"), while the included text compiles to the code the kernel had with the loop written out in it.
+// kBTerms: the terms of the image (scan_pass.inc) - 2 for f32 queries, ScanElem<E>::kTerms for the self-join.
 // ------------------------------------------------------------------------------------------
-template <typename E, bool ALIGNED>
+template <typename E, bool ALIGNED, int kBTerms = 2>
 __device__ __forceinline__ void scan_pass(const typename ScanElem<E>::T* __restrict__ corpus, int64_t ldc, int dim, int nchunks,
                                           const int64_t* __restrict__ row_ids, const u32x4* __restrict__ bimg, u32x4* bl,
                                           int64_t base, int64_t row_begin, int64_t row_end, int tid, bool (&live)[2],
@@ -489,6 +495,184 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_above_kernel(const typen
 }
 
 // ------------------------------------------------------------------------------------------
+// self-join (scan_pairs_kernel, lshrs_scan_pairs_*): the queries are a block [qb, qb + qn) of the stored rows themselves.
+// The image and the norms come straight from the rows - each element converted to f32 exactly, then split and summed as
+// scan_prep_kernel and scan_qnorm_kernel split and sum an f32 query - so an approximate score is the one lshrs_scan_above_*
+// gives the same rows as f32 queries.  A one-term row is exact in bf16: its mid term is zero, the image holds hi only
+// (half the bytes) and the pass issues no MFMA for it (scan_pass.inc, kBTerms = 1).  A dead row, like a padding query, gets a
+// zero image and a norm of 1 and sets no error bit; the pairs kernel gives it a bar of +inf.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ float scan_elem_f32(float, float v) { return v; }
+__device__ __forceinline__ float scan_elem_f32(Bf16, uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
+__device__ __forceinline__ float scan_elem_f32(F16, uint16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
+__device__ __forceinline__ float scan_elem_f32(I8, int8_t v) { return (float)v; }
+__device__ __forceinline__ float scan_elem_f32(F8E4M3, uint8_t v) { return __builtin_amdgcn_cvt_f32_fp8((int)v, 0); }
+
+// image: [qtile][chunk][term < kTerms][step s][column block cb][lane] x 16 bytes, the lanes as in scan_prep_kernel
+template <typename E>
+__global__ __launch_bounds__(kScanThreads) void scan_pairs_prep_kernel(const typename ScanElem<E>::T* __restrict__ corpus,
+                                                                       int64_t ldc, int dim, const int64_t* __restrict__ row_ids,
+                                                                       int64_t qb, int qn, int nchunks, u32x4* __restrict__ image) {
+  constexpr int kBTerms = ScanElem<E>::kTerms;
+  const int chunk = blockIdx.x, qtile = blockIdx.y;
+  u32x4* out = image + ((int64_t)qtile * nchunks + chunk) * (kBTerms * 512);
+  for (int f = threadIdx.x; f < 512; f += kScanThreads) {
+    const int lane = f & 63, cb = (f >> 6) & 1, s = f >> 7;
+    const int qi = qtile * kScanQTile + cb * 32 + (lane & 31);
+    const bool ok = qi < qn && (row_ids == nullptr || row_ids[qb + qi] >= 0);
+    const typename ScanElem<E>::T* row = corpus + (qb + (ok ? qi : 0)) * ldc;
+    const int kbase = chunk * kScanKChunk + 32 * (lane >> 5) + 8 * s;
+    uint32_t hb[8], mb[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int k = kbase + j;
+      const float v = (ok && k < dim) ? scan_elem_f32(E{}, row[k]) : 0.f;
+      const uint32_t b = __float_as_uint(v) & 0xffff0000u;
+      hb[j] = b >> 16;
+      mb[j] = __float_as_uint(v - __uint_as_float(b)) >> 16;
+    }
+    u32x4 hi, mid;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      hi[d] = hb[2 * d] | (hb[2 * d + 1] << 16);
+      mid[d] = mb[2 * d] | (mb[2 * d + 1] << 16);
+    }
+    out[((0 * 4 + s) * 2 + cb) * 64 + lane] = hi;
+    if constexpr (kBTerms == 2) out[((1 * 4 + s) * 2 + cb) * 64 + lane] = mid;
+  }
+}
+
+// ||row|| in f32 in scan_qnorm_kernel's order, one wave per query row of the block (1 for a dead or a padding one); err |= 4
+// for a live row of zero norm
+template <typename E>
+__global__ __launch_bounds__(kScanThreads) void scan_pairs_qnorm_kernel(const typename ScanElem<E>::T* __restrict__ corpus,
+                                                                        int64_t ldc, int dim, const int64_t* __restrict__ row_ids,
+                                                                        int64_t qb, int qn, int qpad, float* __restrict__ qnorm,
+                                                                        int32_t* __restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int qi = blockIdx.x * kScanWaves + (threadIdx.x >> 6);
+  if (qi >= qpad) return;
+  const bool ok = qi < qn && (row_ids == nullptr || row_ids[qb + qi] >= 0);
+  float ss = 0.f;
+  if (ok) {
+    const typename ScanElem<E>::T* row = corpus + (qb + qi) * ldc;
+    for (int k = lane; k < dim; k += 64) {
+      const float v = scan_elem_f32(E{}, row[k]);
+      ss = __builtin_fmaf(v, v, ss);
+    }
+  }
+  ss = scan_wave_sum(ss);
+  if (lane == 0) {
+    const float n = ok ? sqrtf(ss) : 1.f;
+    qnorm[qi] = n;
+    if (n == 0.f && err != nullptr) atomicOr(err, 4);
+  }
+}
+
+// One workgroup per CU: at two, this kernel - like scan_above_kernel - fills 256 VGPRs and spills a few loop invariants to
+// scratch; at one the accumulators live in AGPRs and nothing is spilled (self-join).
+constexpr int kScanPairsPerCu = 1;
+
+// grid (slices of the rows [qb, m), query tiles of the block): scan_above_kernel's pass and emitter.  A pair (a, b) goes out
+// when a is a live row of the tile, b a live row with b > a (by position: every unordered pair once, no row against itself)
+// and approx >= bar.  The workgroup starts at the pass that holds its tile's first row: no pass whose rows all lie before it.
+template <typename E, bool ALIGNED>
+__global__ __launch_bounds__(kScanThreads, kScanPairsPerCu) void scan_pairs_kernel(const typename ScanElem<E>::T* __restrict__ corpus, int64_t m,
+                                                                  int64_t ldc, int dim, const int64_t* __restrict__ row_ids,
+                                                                  const u32x4* __restrict__ image,
+                                                                  const float* __restrict__ qnorm, float bar_all, int64_t qb,
+                                                                  int qn, int64_t rows_per_slice, int64_t capacity,
+                                                                  int64_t* __restrict__ out_a, int64_t* __restrict__ out_b,
+                                                                  float* __restrict__ out_approx,
+                                                                  unsigned long long* __restrict__ total,
+                                                                  int32_t* __restrict__ err) {
+  constexpr int kBTerms = ScanElem<E>::kTerms;
+  extern __shared__ __attribute__((aligned(16))) unsigned char scan_lds[];
+  u32x4* bl = reinterpret_cast<u32x4*>(scan_lds);
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int r = lane & 31, h = lane >> 5;
+  const int slice = blockIdx.x, qtile = blockIdx.y;
+  const int nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
+  const int64_t row_begin = qb + (int64_t)slice * rows_per_slice;
+  const int64_t row_end = min(m, row_begin + rows_per_slice);
+  const int64_t tile_first = qb + (int64_t)qtile * kScanQTile;
+  const int64_t first_base = tile_first <= row_begin ? row_begin
+                                                     : row_begin + (tile_first - row_begin) / kScanPassRows * kScanPassRows;
+  if (first_base >= row_end) return;      // (the whole slice lies before the tile; uniform, nothing was synchronised yet)
+  const u32x4* bimg = image + (int64_t)qtile * nchunks * (kBTerms * 512);
+
+  // the lane's query rows are tile_first + cb * 32 + r; which of them exist and are live, as wave masks (kept out of the
+  // vector registers, as everything here that outlives a pass is: the pass needs them all)
+  float qnv[2];
+  uint64_t qlive[2];
+#pragma unroll
+  for (int cb = 0; cb < 2; ++cb) {
+    const int qi = qtile * kScanQTile + cb * 32 + r;
+    qnv[cb] = qnorm[qi];                  // (padded to whole tiles)
+    qlive[cb] = __ballot(qi < qn && (row_ids == nullptr || row_ids[qb + qi] >= 0));
+  }
+
+  for (int64_t base = first_base; base < row_end; base += kScanPassRows) {
+    bool live[2];
+    int64_t row0[2];
+    f32x16 acc[2][2];
+    float nn[2];
+    scan_pass<E, ALIGNED, kBTerms>(corpus, ldc, dim, nchunks, row_ids, bimg, bl, base, row_begin, row_end, tid, live, row0, acc,
+                                   nn);
+
+    // the finished 256 x 64 tile: acc[t][cb][i] is row (i & 3) + 8 (i >> 2) + 4 h of tile t, query row cb * 32 + r of the tile
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      nn[t] += __shfl_xor(nn[t], 32);
+      const float xn = sqrtf(nn[t]);
+      if (live[t] && xn == 0.f && h == 0 && err != nullptr) atomicOr(err, 1);
+      const uint32_t livemask = (uint32_t)__ballot(live[t]);
+      uint32_t hits = 0;                  // bit cb * 16 + i
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        // nothing reaches the bar of a dead or a padding row (NaN reaches none); rows of this tile at or before the lane's
+        // query row are not its partners: b > a <=> the row's offset in the tile > gap (diagonal tiles; else -1: all are)
+        const float bar = ((qlive[cb] >> lane) & 1ull) ? bar_all : __builtin_inff();
+        const int64_t ahead = tile_first + cb * 32 - row0[t];          // (uniform)
+        const int gap = ahead < -32 ? -1 : ahead > 32 ? 32 : (int)ahead + r;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int rr = (i & 3) + 8 * (i >> 2) + 4 * h;
+          const float rn = __shfl(xn, rr);
+          const float sc = acc[t][cb][i] / (rn * qnv[cb]);
+          acc[t][cb][i] = sc;
+          if (((livemask >> rr) & 1u) && rr > gap && sc >= bar) hits |= 1u << (cb * 16 + i);
+        }
+      }
+      if (__ballot(hits != 0) == 0ull) continue;        // (the common case: nothing of this tile reaches the bar)
+      const int mine = __popc(hits);
+      int incl = mine;                    // inclusive prefix sum of the lanes' hit counts
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
+      }
+      unsigned long long first = 0ull;
+      if (lane == 63) first = atomicAdd(total, (unsigned long long)incl);     // (lane 63's sum is the wave's)
+      int64_t slot = (int64_t)__shfl(first, 63) + (incl - mine);
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (hits & (1u << (cb * 16 + i))) {
+            if (slot < capacity) {
+              out_a[slot] = tile_first + cb * 32 + r;
+              out_b[slot] = row0[t] + (i & 3) + 8 * (i >> 2) + 4 * h;
+              out_approx[slot] = acc[t][cb][i];
+            }
+            ++slot;
+          }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // one workgroup per query: the slices' winners into LDS, bitonic network descending, the first `window` out
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kScanThreads) void scan_merge_kernel(const uint64_t* __restrict__ parts, int n, int npad, int window,
@@ -538,9 +722,10 @@ struct ScanPlan {
 
 // slices: one round of the workgroups that are resident at a time - 256 CUs, two per CU while their LDS (`lds` bytes) fits twice
 // into the CU's 160 KiB, else one - over all query tiles: a second, part-filled round costs a whole slice's time.  At least
-// 1024 rows each, and no more than `limit` (scan_kernel: what one merge workgroup sorts in LDS).
-inline void scan_slices(int64_t m, int qtiles, int64_t lds, int64_t limit, int64_t& rows_per_slice, int& slices) {
-  const int64_t resident = 256 * (2 * lds <= 160 * 1024 ? 2 : 1);
+// 1024 rows each, and no more than `limit` (scan_kernel: what one merge workgroup sorts in LDS).  `per_cu`: the workgroups per CU
+// the kernel is compiled for (its __launch_bounds__).
+inline void scan_slices(int64_t m, int qtiles, int64_t lds, int64_t limit, int64_t& rows_per_slice, int& slices, int per_cu = 2) {
+  const int64_t resident = 256 * (per_cu >= 2 && 2 * lds <= 160 * 1024 ? 2 : 1);
   const int64_t qt = qtiles > 0 ? qtiles : 1;
   int64_t want = resident / qt;
   const int64_t by_rows = (m + 1023) / 1024;
@@ -685,6 +870,83 @@ int scan_above(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, in
                        f.image, f.qnorm, bars, q, p.rows_per_slice, capacity, out_query, out_row, out_approx, cursor, err);
   return -(int)hipGetLastError();
 }
+
+// self-join: the rows are taken as queries a block at a time.  The plan's block: 128 query tiles - with the rows in two
+// slices, one round of the 256 workgroups resident at a time, every slice's rows read by 128 of them in step - fewer where the
+// image of that many (at two terms, whatever the rows hold: the workspace's size knows no element type) would pass 256 MiB or
+// the rows end.  A caller's block (a multiple of 64) is taken as it is.
+constexpr int kScanPairsBlock = 8192;
+constexpr int64_t kScanPairsImageBytes = 256ll << 20;
+
+struct ScanPairsPlan {
+  int qblock, nchunks;
+  int64_t image_bytes, qnorm_bytes;
+};
+
+inline int scan_pairs_plan(int64_t m, int32_t dim, int32_t qblock, ScanPairsPlan& p) {
+  if (m <= 0 || dim <= 0 || qblock < 0 || qblock % kScanQTile) return LSHRS_E_BADARG;
+  if (dim > kScanMaxDim || m > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
+  p.nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
+  const int64_t tile_bytes = (int64_t)p.nchunks * kScanChunkBytes;
+  int64_t tiles = qblock / kScanQTile;
+  if (qblock == 0) {
+    tiles = kScanPairsBlock / kScanQTile;
+    if (tiles > kScanPairsImageBytes / tile_bytes) tiles = kScanPairsImageBytes / tile_bytes;     // (at least 64: 4 MiB a tile)
+    if (tiles > (m + kScanQTile - 1) / kScanQTile) tiles = (m + kScanQTile - 1) / kScanQTile;
+  }
+  if (tiles > 65535) return LSHRS_E_TOOLARGE;
+  p.qblock = (int)tiles * kScanQTile;
+  p.image_bytes = tiles * tile_bytes;
+  p.qnorm_bytes = tiles * kScanQTile * (int64_t)sizeof(float);
+  return 0;
+}
+
+template <typename E>
+int scan_pairs(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
+               int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
+               void* workspace, int32_t* err, void* stream) {
+  constexpr int kBTerms = ScanElem<E>::kTerms;
+  ScanPairsPlan p;
+  const int bad = scan_pairs_plan(m, dim, qblock, p);
+  if (bad) return bad;
+  const auto addr = [](const void* ptr) { return reinterpret_cast<uintptr_t>(ptr); };
+  if (corpus == nullptr || total == nullptr || workspace == nullptr || capacity < 0 ||
+      (capacity > 0 && (out_a == nullptr || out_b == nullptr || out_approx == nullptr)) || (addr(workspace) & 15) ||
+      (addr(total) & 7) || (addr(out_a) & 7) || (addr(out_b) & 7) || (addr(out_approx) & 3) || (addr(row_ids) & 7) || ldc < dim)
+    return LSHRS_E_BADARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const hipError_t e = hipMemsetAsync(total, 0, sizeof(uint64_t), s);
+  if (e != hipSuccess) return -(int)e;
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  u32x4* image = reinterpret_cast<u32x4*>(ws);
+  float* qnorm = reinterpret_cast<float*>(ws + p.image_bytes);
+  const bool aligned = (ldc % ScanElem<E>::kAlign == 0) && ((addr(corpus) & 15) == 0);
+  unsigned long long* cursor = reinterpret_cast<unsigned long long*>(total);
+  const size_t lds = (size_t)kBTerms * (kScanChunkBytes / 2);
+  const dim3 block(kScanThreads);
+  // the blocks one after the other on the stream: they share the image, the norms and the cursor
+  for (int64_t qb = 0; qb < m; qb += p.qblock) {
+    const int qn = (int)(m - qb < p.qblock ? m - qb : p.qblock);
+    const int qtiles = (qn + kScanQTile - 1) / kScanQTile, qpad = qtiles * kScanQTile;
+    int64_t rows_per_slice;
+    int slices;
+    scan_slices(m - qb, qtiles, (int64_t)lds, INT64_MAX, rows_per_slice, slices, kScanPairsPerCu);
+    hipLaunchKernelGGL((scan_pairs_prep_kernel<E>), dim3((unsigned)p.nchunks, (unsigned)qtiles), block, 0, s, corpus, ldc, dim,
+                       row_ids, qb, qn, p.nchunks, image);
+    hipLaunchKernelGGL((scan_pairs_qnorm_kernel<E>), dim3((unsigned)(qpad / kScanWaves)), block, 0, s, corpus, ldc, dim, row_ids,
+                       qb, qn, qpad, qnorm, err);
+    const dim3 grid((unsigned)slices, (unsigned)qtiles);
+    if (aligned)
+      hipLaunchKernelGGL((scan_pairs_kernel<E, true>), grid, block, lds, s, corpus, m, ldc, dim, row_ids, image, qnorm, bar, qb,
+                         qn, rows_per_slice, capacity, out_a, out_b, out_approx, cursor, err);
+    else
+      hipLaunchKernelGGL((scan_pairs_kernel<E, false>), grid, block, lds, s, corpus, m, ldc, dim, row_ids, image, qnorm, bar, qb,
+                         qn, rows_per_slice, capacity, out_a, out_b, out_approx, cursor, err);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return -(int)le;
+  }
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -779,6 +1041,48 @@ int lshrs_scan_above_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32
                          uint64_t* total, void* workspace, int32_t* err, void* stream) {
   return scan_above<F8E4M3>(corpus, m, ldc, dim, row_ids, queries, q, bars, capacity, out_query, out_row, out_approx, total, workspace,
                         err, stream);
+}
+
+int64_t lshrs_scan_pairs_workspace_bytes(int64_t m, int32_t dim, int32_t qblock) {
+  ScanPairsPlan p;
+  const int bad = scan_pairs_plan(m, dim, qblock, p);
+  if (bad) return bad;
+  return p.image_bytes + p.qnorm_bytes + 16;
+}
+
+int lshrs_scan_pairs_f32(const float* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
+                          int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
+                          void* workspace, int32_t* err, void* stream) {
+  return scan_pairs<float>(corpus, m, ldc, dim, row_ids, bar, qblock, capacity, out_a, out_b, out_approx, total, workspace, err,
+                         stream);
+}
+
+int lshrs_scan_pairs_bf16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
+                          int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
+                          void* workspace, int32_t* err, void* stream) {
+  return scan_pairs<Bf16>(corpus, m, ldc, dim, row_ids, bar, qblock, capacity, out_a, out_b, out_approx, total, workspace, err,
+                         stream);
+}
+
+int lshrs_scan_pairs_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
+                          int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
+                          void* workspace, int32_t* err, void* stream) {
+  return scan_pairs<F16>(corpus, m, ldc, dim, row_ids, bar, qblock, capacity, out_a, out_b, out_approx, total, workspace, err,
+                         stream);
+}
+
+int lshrs_scan_pairs_i8(const int8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
+                          int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
+                          void* workspace, int32_t* err, void* stream) {
+  return scan_pairs<I8>(corpus, m, ldc, dim, row_ids, bar, qblock, capacity, out_a, out_b, out_approx, total, workspace, err,
+                         stream);
+}
+
+int lshrs_scan_pairs_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
+                          int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
+                          void* workspace, int32_t* err, void* stream) {
+  return scan_pairs<F8E4M3>(corpus, m, ldc, dim, row_ids, bar, qblock, capacity, out_a, out_b, out_approx, total, workspace, err,
+                         stream);
 }
 
 }  // extern "C"

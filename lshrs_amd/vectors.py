@@ -373,6 +373,19 @@ class DeviceVectors:
 
         return self._search(exact_above, queries, threshold, max_pairs=max_pairs, return_tensors=return_tensors)
 
+    def pairs_above(self, threshold, *, max_pairs: int = 1 << 26, return_tensors: bool = False):
+        """Every pair of stored vectors at or above a cosine ``threshold`` (one number), exactly, under the caller's ids:
+        ``(ids_a (p,) int64, ids_b (p,) int64, scores (p,) float32)``, ``ids_a < ids_b``, scores descending -
+        :func:`lshrs_amd.exact_pairs_above` over the row block where it is, superseded and erased rows left out.  What the call
+        did (rows, pairs the first pass let through, pairs kept, launches, blocks, epsilon) is left in ``last_search_stats``."""
+        from ._exact import exact_pairs_above
+
+        rows, row_ids = self._search_snapshot()
+        stats: Dict[str, Any] = {}
+        got = exact_pairs_above(rows, threshold, row_ids=row_ids, max_pairs=max_pairs, return_tensors=return_tensors, stats=stats)
+        self.last_search_stats = stats
+        return got
+
     def _search(self, fn, queries, what, **kwargs):
         """``fn`` (``exact_top_k`` / ``exact_above``) of ``queries`` and ``what`` (its ``k`` / ``threshold``) over one snapshot
         of the row block and its row -> id list; what it did goes to ``last_search_stats``."""
