@@ -115,6 +115,62 @@ def _scan_workspace(torch, lib, sizer: str, dev, *shape):
     return torch.empty(nbytes, dtype=torch.uint8, device=dev)
 
 
+def _scan_emitting(corpus, family: str, first_dtype, capacity: int, empty: bool, sizer_shape, head, row_ids):
+    """The plumbing of the two emitting entries (``family``: "above" or "pairs"): three output arrays of ``capacity`` slots -
+    the first of ``first_dtype`` - a cursor and the error bits; unless ``empty``, the workspace (``sizer_shape``: what
+    ``lshrs_scan_<family>_workspace_bytes`` takes) and the launch, ``head`` being the entry's own arguments between ``row_ids``
+    and ``capacity``.  No output pointer is passed for a ``capacity`` of 0.  Returns ``(first, second, approx, total, err)``."""
+    torch = _native.require_gpu()
+    lib = _native.load()
+    entry = f"lshrs_scan_{family}_" + corpus_suffix(corpus)
+    dev = corpus.device
+    capacity = int(capacity)
+    first = torch.empty((capacity,), dtype=first_dtype, device=dev)
+    second = torch.empty((capacity,), dtype=torch.int64, device=dev)
+    approx = torch.empty((capacity,), dtype=torch.float32, device=dev)
+    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    if empty:
+        return first, second, approx, total, err
+    with torch.cuda.device(dev):
+        ws = _scan_workspace(torch, lib, f"lshrs_scan_{family}_workspace_bytes", dev, *sizer_shape)
+        outs = [t.data_ptr() if capacity else None for t in (first, second, approx)]
+        _native.check(getattr(lib, entry)(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)), int(corpus.shape[1]),
+                                          row_ids.data_ptr() if row_ids is not None else None, *head, capacity, *outs,
+                                          total.data_ptr(), ws.data_ptr(), err.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream), entry)
+    return first, second, approx, total, err
+
+
+def _all_pairs(launch, first_capacity: int, max_pairs: int, caller: str, out: Dict):
+    """The capacity protocol of ``exact_above`` and ``exact_pairs_above`` (``caller``: the name the messages carry):
+    ``launch(capacity)`` - ``scan_above`` or ``scan_pairs`` with everything else bound - once with ``first_capacity`` slots
+    and, when more pairs reached the bar, a second time with room for all.  One number crosses to the host per launch: how
+    many pairs the pass found.  Returns ``(first, second, emitted)`` and records ``launches`` and ``emitted`` in ``out``."""
+    first, second, _, total, err = launch(first_capacity)
+    emitted = int(total.item())
+    out["launches"] = 1
+    if int(err.item()) & 5:
+        raise ValueError("Cannot normalize zero vector")
+    if emitted > max_pairs:
+        raise ValueError(f"{caller}: {emitted} pairs reach the threshold's bar, more than max_pairs = {max_pairs}")
+    if emitted > first_capacity:
+        del first, second
+        first, second, _, total, err = launch(emitted)
+        out["launches"] = 2
+        if int(total.item()) != emitted:            # (the same launches on the same data: the same count)
+            raise RuntimeError(f"{caller}: the second pass counted other pairs than the first")
+    out["emitted"] = emitted
+    return first, second, emitted
+
+
+def _descending(torch, scores):
+    """An int64 in [0, 2^32) that DEscends with a float32 score (-0.0 with 0.0): a stable ascending sort on it orders by
+    descending score and keeps the order of equal scores."""
+    bits = (scores + 0.0).view(torch.int32)
+    return 0x7FFFFFFF - torch.where(bits >= 0, bits, bits ^ 0x7FFFFFFF).long()
+
+
 def scan_windows(corpus, queries, window: int, row_ids=None):
     """Device-level entry of the first pass: ``corpus`` (m, dim) as ``corpus_suffix`` accepts it, ``queries`` (q, dim) float32
     contiguous on the same device, ``row_ids`` optional int64 (m,) there.  Returns ``(rows (q, window) int64, approx (q, window)
@@ -290,10 +346,14 @@ def exact_top_k(queries, corpus, k: int, *, row_ids=None, method: str = "auto", 
 # ------------------------------------------------------------------------------------------
 # range search: every live row at or above a cosine threshold
 # ------------------------------------------------------------------------------------------
-def _check_above_args(q: int, threshold, max_pairs) -> np.ndarray:
-    """The thresholds of ``q`` queries as float64 ``(q,)``; ``ValueError`` for what ``exact_above`` does not take.  Pure host."""
+def _check_max_pairs(max_pairs) -> None:
     if int(max_pairs) < 0:
         raise ValueError(f"max_pairs must be >= 0; received {max_pairs}")
+
+
+def _check_above_args(q: int, threshold, max_pairs) -> np.ndarray:
+    """The thresholds of ``q`` queries as float64 ``(q,)``; ``ValueError`` for what ``exact_above`` does not take.  Pure host."""
+    _check_max_pairs(max_pairs)
     try:
         t = np.asarray(threshold, dtype=np.float64)
     except (TypeError, ValueError) as exc:
@@ -328,27 +388,9 @@ def scan_above(corpus, queries, bars, capacity: int, row_ids=None):
     (capacity,) int64, approx (capacity,) float32, total uint64-as-int64[1], err int32[1])``: the first ``min(total,
     capacity)`` slots are pairs, in no particular order; ``total`` counts every pair that reached its bar."""
     torch = _native.require_gpu()
-    lib = _native.load()
-    entry = "lshrs_scan_above_" + corpus_suffix(corpus)
-    dev = corpus.device
     q, m, dim = int(queries.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
-    capacity = int(capacity)
-    out_q = torch.empty((capacity,), dtype=torch.int32, device=dev)
-    out_row = torch.empty((capacity,), dtype=torch.int64, device=dev)
-    out_approx = torch.empty((capacity,), dtype=torch.float32, device=dev)
-    total = torch.zeros(1, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    if q == 0:
-        return out_q, out_row, out_approx, total, err
-    with torch.cuda.device(dev):
-        ws = _scan_workspace(torch, lib, "lshrs_scan_above_workspace_bytes", dev, q, m, dim)
-        _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim,
-                                          row_ids.data_ptr() if row_ids is not None else None, queries.data_ptr(), q,
-                                          bars.data_ptr(), capacity, out_q.data_ptr() if capacity else None,
-                                          out_row.data_ptr() if capacity else None, out_approx.data_ptr() if capacity else None,
-                                          total.data_ptr(), ws.data_ptr(), err.data_ptr(),
-                                          torch.cuda.current_stream(dev).cuda_stream), entry)
-    return out_q, out_row, out_approx, total, err
+    return _scan_emitting(corpus, "above", torch.int32, capacity, q == 0, (q, m, dim),
+                          (queries.data_ptr(), q, bars.data_ptr()), row_ids)
 
 
 def exact_above(queries, corpus, threshold, *, row_ids=None, max_pairs: int = 1 << 26, return_tensors: bool = False,
@@ -391,20 +433,8 @@ def exact_above(queries, corpus, threshold, *, row_ids=None, max_pairs: int = 1 
             bars = torch.from_numpy(above_bars(thr64, eps + rerank_rounding(dim))).to(dev)
             t32 = torch.from_numpy(thr64.astype(np.float32)).to(dev)
             capacity = min(max(_ABOVE_FIRST_CAPACITY, 64 * q), max_pairs)
-            pq, prow, _, total, err = scan_above(corpus, d_q, bars, capacity, d_ids)
-            emitted = int(total.item())                 # (the one size that crosses to the host)
-            out["launches"] = 1
-            if int(err.item()) & 5:
-                raise ValueError("Cannot normalize zero vector")
-            if emitted > max_pairs:
-                raise ValueError(f"exact_above: {emitted} pairs reach the threshold's bar, more than max_pairs = {max_pairs}")
-            if emitted > capacity:
-                del pq, prow
-                pq, prow, _, total, err = scan_above(corpus, d_q, bars, emitted, d_ids)
-                out["launches"] = 2
-                if int(total.item()) != emitted:        # (the same launch on the same data: the same count)
-                    raise RuntimeError("exact_above: the second pass counted other pairs than the first")
-            out["emitted"] = emitted
+            pq, prow, emitted = _all_pairs(lambda cap: scan_above(corpus, d_q, bars, cap, d_ids), capacity, max_pairs,
+                                           "exact_above", out)
             if emitted:
                 # by query (stable), then the rerank's own score of every pair: its lists are the queries' runs
                 pq, by_q = torch.sort(pq[:emitted].long(), stable=True)
@@ -421,9 +451,7 @@ def exact_above(queries, corpus, threshold, *, row_ids=None, max_pairs: int = 1 
                 # descends with the score (-0.0 with 0.0)} orders every query's run by descending score, ties by the id order
                 _, order = torch.sort(pid, stable=True)
                 pq, exact, pid = pq[order], exact[order], pid[order]
-                bits = (exact + 0.0).view(torch.int32)
-                down = 0x7FFFFFFF - torch.where(bits >= 0, bits, bits ^ 0x7FFFFFFF).long()     # in [0, 2^32)
-                _, order = torch.sort((pq << 32) | down, stable=True)
+                _, order = torch.sort((pq << 32) | _descending(torch, exact), stable=True)
                 pq, exact, pid = pq[order], exact[order], pid[order]
                 ids, scores = pid.contiguous(), exact.contiguous()
                 bounds[1:] = torch.cumsum(torch.bincount(pq, minlength=q), 0)
@@ -441,26 +469,9 @@ def scan_pairs(corpus, bar: float, capacity: int, row_ids=None, qblock: int = 0)
     total uint64-as-int64[1], err int32[1])``: the first ``min(total, capacity)`` slots are pairs of row POSITIONS, ``a < b``,
     in no particular order; ``total`` counts every pair that reached the bar."""
     torch = _native.require_gpu()
-    lib = _native.load()
-    entry = "lshrs_scan_pairs_" + corpus_suffix(corpus)
-    dev = corpus.device
     m, dim = int(corpus.shape[0]), int(corpus.shape[1])
-    capacity = int(capacity)
-    out_a = torch.empty((capacity,), dtype=torch.int64, device=dev)
-    out_b = torch.empty((capacity,), dtype=torch.int64, device=dev)
-    out_approx = torch.empty((capacity,), dtype=torch.float32, device=dev)
-    total = torch.zeros(1, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    if m == 0:
-        return out_a, out_b, out_approx, total, err
-    with torch.cuda.device(dev):
-        ws = _scan_workspace(torch, lib, "lshrs_scan_pairs_workspace_bytes", dev, m, dim, int(qblock))
-        _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim,
-                                          row_ids.data_ptr() if row_ids is not None else None, float(bar), int(qblock), capacity,
-                                          out_a.data_ptr() if capacity else None, out_b.data_ptr() if capacity else None,
-                                          out_approx.data_ptr() if capacity else None, total.data_ptr(), ws.data_ptr(),
-                                          err.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), entry)
-    return out_a, out_b, out_approx, total, err
+    return _scan_emitting(corpus, "pairs", torch.int64, capacity, m == 0, (m, dim, int(qblock)), (float(bar), int(qblock)),
+                          row_ids)
 
 
 def _pairs_block(lib, m: int, dim: int) -> int:
@@ -481,9 +492,9 @@ def _rows_as_f32(torch, corpus, rows):
 
 
 def _check_pairs_args(threshold, max_pairs) -> float:
-    """The threshold of ``exact_pairs_above`` as a float; ``ValueError`` for what it does not take.  Pure host."""
-    if int(max_pairs) < 0:
-        raise ValueError(f"max_pairs must be >= 0; received {max_pairs}")
+    """The threshold of ``exact_pairs_above`` as a float; ``ValueError`` for what it does not take: a negative ``max_pairs``
+    first, as everywhere; then what is not ONE number; then all that :func:`_check_above_args` refuses.  Pure host."""
+    _check_max_pairs(max_pairs)
     try:
         t = np.asarray(threshold, dtype=np.float64)
     except (TypeError, ValueError) as exc:
@@ -537,21 +548,8 @@ def exact_pairs_above(corpus, threshold, *, row_ids=None, max_pairs: int = 1 << 
             t32 = float(np.float32(t))
             out["blocks"] = -(-m // _pairs_block(lib, m, dim))
             capacity = min(_PAIRS_FIRST_CAPACITY, max_pairs)
-            pa, pb, _, total, err = scan_pairs(corpus, bar, capacity, d_ids)
-            emitted = int(total.item())                 # (the one size that crosses to the host)
-            out["launches"] = 1
-            if int(err.item()) & 5:
-                raise ValueError("Cannot normalize zero vector")
-            if emitted > max_pairs:
-                raise ValueError(f"exact_pairs_above: {emitted} pairs reach the threshold's bar, more than max_pairs = "
-                                 f"{max_pairs}")
-            if emitted > capacity:
-                del pa, pb
-                pa, pb, _, total, err = scan_pairs(corpus, bar, emitted, d_ids)
-                out["launches"] = 2
-                if int(total.item()) != emitted:        # (the same launches on the same data: the same count)
-                    raise RuntimeError("exact_pairs_above: the second pass counted other pairs than the first")
-            out["emitted"] = emitted
+            pa, pb, emitted = _all_pairs(lambda cap: scan_pairs(corpus, bar, cap, d_ids), capacity, max_pairs,
+                                         "exact_pairs_above", out)
             if emitted:
                 pa, pb = pa[:emitted], pb[:emitted]
                 # the orientation is by id: the row of the lower id asks, the row of the higher id is scored
@@ -586,9 +584,7 @@ def exact_pairs_above(corpus, threshold, *, row_ids=None, max_pairs: int = 1 << 
                 ia, ib, exact = ia[order], ib[order], exact[order]
                 _, order = torch.sort(ia, stable=True)
                 ia, ib, exact = ia[order], ib[order], exact[order]
-                bits = (exact + 0.0).view(torch.int32)
-                down = 0x7FFFFFFF - torch.where(bits >= 0, bits, bits ^ 0x7FFFFFFF).long()     # in [0, 2^32)
-                _, order = torch.sort(down, stable=True)
+                _, order = torch.sort(_descending(torch, exact), stable=True)
                 ids_a, ids_b, scores = ia[order].contiguous(), ib[order].contiguous(), exact[order].contiguous()
                 out["kept"] = int(ids_a.shape[0])
     return _finish(stats, out, (ids_a, ids_b, scores), return_tensors)

@@ -7,7 +7,7 @@
 // tiles.  The rows are the A operand, read from global memory straight into the registers the instruction wants (a lane's
 // eight k-values of one row are contiguous: no LDS); the queries are the B operand, split once per launch into two bf16
 // terms (hi = the f32's upper 16 bits, mid = the upper 16 bits of q - hi) and laid out in fragment order by
-// scan_prep_kernel, staged through LDS in chunks of 64 k so that any dim fits.  Within a chunk the lanes' halves take k in
+// scan_image_kernel, staged through LDS in chunks of 64 k so that any dim fits.  Within a chunk the lanes' halves take k in
 // [32h, 32h + 32): MFMA step s multiplies k = 32h + 8s + j on both operands - a permutation of k, which a sum over k does not
 // see - so that a lane's 32 elements of a row are ONE contiguous run (64 bytes of bf16).
 // bf16, int8 and e4m3fn rows are exact in bf16 (one term); f16 and f32 rows enter as two terms (x_hi q_hi + x_hi q_mid +
@@ -21,10 +21,14 @@
 // Range scan (scan_above_kernel, lshrs_scan_above_*): the same first pass with no selection at all - every (query, live row)
 // whose approximate score reaches the query's bar is emitted to flat arrays through one global cursor (lshrs_amd.exact_above).
 // Self-join (scan_pairs_kernel, lshrs_scan_pairs_*): the range scan with a block of the stored rows themselves as the queries -
-// image and norms built straight from the rows (scan_pairs_prep_kernel, scan_pairs_qnorm_kernel), every unordered pair of live
-// rows multiplied once (a block scans the rows from its own first row on, a workgroup from its tile's; diagonal tiles masked
-// lane by lane), one MFMA per step for the one-term types, whose image holds no mid term (lshrs_amd.exact_pairs_above).
-// The pass (rows in, dot products and norms out) is written once, in scan_pass.inc, and compiled into all three kernels.
+// image and norms built straight from the rows, every unordered pair of live rows multiplied once (a block scans the rows from
+// its own first row on, a workgroup from its tile's; diagonal tiles masked lane by lane), one MFMA per step for the one-term
+// types, whose image holds no mid term (lshrs_amd.exact_pairs_above).
+// Every layer is written once.  All three kernels: the image and the norms of the queries, whatever they are made of
+// (scan_image_kernel<Q>, scan_norm_kernel<Q>, launched by scan_front), the pass - rows in, dot products and norms out
+// (scan_pass.inc) - and the head of a finished tile (scan_tile_head).  The two emitting kernels: scoring and marking a tile
+// (scan_mark) and writing its hits through the cursor (scan_emit); on the host their common refusals and the cursor's reset
+// (scan_emit_begin).  The three plans: scan_rows_geometry and scan_front_bytes.
 // ABI and reference citations: include/lshrs_hip.h.  Design notes, the epsilon derivation and the roof: DESIGN.md.
 #include "lshrs_common.h"
 
@@ -75,22 +79,38 @@ __device__ __forceinline__ float scan_unkey(uint32_t k) {
 }
 
 // ------------------------------------------------------------------------------------------
-// queries -> B fragments.  Workspace image: [qtile][chunk][term][step s][column block cb][lane] x 16 bytes; lane (c = l & 31,
-// h = l >> 5) holds query qtile * 64 + cb * 32 + c at k = chunk * 64 + 32 h + 8 s + j, j = 0 .. 7.  Zero beyond q and dim.
+// queries -> B fragments and norms, one text for both kinds of query: rows of f32 (the `float` instantiation: src = the
+// queries, ld = dim, row_ids = nullptr, qb = 0, qn = q) and a block [qb, qb + qn) of the stored rows themselves (the
+// self-join: src = the corpus, its ld and row_ids).  An element is converted to f32 exactly, then split and summed in one
+// order whatever it was, so an approximate score of the self-join is the one the same rows get as f32 queries.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kScanThreads) void scan_prep_kernel(const float* __restrict__ queries, int q, int dim, int nchunks,
-                                                                 u32x4* __restrict__ image) {
+__device__ __forceinline__ float scan_elem_f32(float, float v) { return v; }
+__device__ __forceinline__ float scan_elem_f32(Bf16, uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
+__device__ __forceinline__ float scan_elem_f32(F16, uint16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
+__device__ __forceinline__ float scan_elem_f32(I8, int8_t v) { return (float)v; }
+__device__ __forceinline__ float scan_elem_f32(F8E4M3, uint8_t v) { return __builtin_amdgcn_cvt_f32_fp8((int)v, 0); }
+
+// Workspace image: [qtile][chunk][term < kTerms][step s][column block cb][lane] x 16 bytes; lane (c = l & 31, h = l >> 5)
+// holds query qtile * 64 + cb * 32 + c at k = chunk * 64 + 32 h + 8 s + j, j = 0 .. 7.  Zero beyond qn and dim, and for a
+// dead row.  A one-term element is exact in bf16: its mid term is zero and the image holds hi only (half the bytes).
+template <typename E>
+__global__ __launch_bounds__(kScanThreads) void scan_image_kernel(const typename ScanElem<E>::T* __restrict__ src, int64_t ld,
+                                                                  int dim, const int64_t* __restrict__ row_ids, int64_t qb, int qn,
+                                                                  int nchunks, u32x4* __restrict__ image) {
+  constexpr int kBTerms = ScanElem<E>::kTerms;
   const int chunk = blockIdx.x, qtile = blockIdx.y;
-  u32x4* out = image + ((int64_t)qtile * nchunks + chunk) * (kScanChunkBytes / 16);
+  u32x4* out = image + ((int64_t)qtile * nchunks + chunk) * (kBTerms * 512);
   for (int f = threadIdx.x; f < 512; f += kScanThreads) {
     const int lane = f & 63, cb = (f >> 6) & 1, s = f >> 7;
     const int qi = qtile * kScanQTile + cb * 32 + (lane & 31);
+    const bool ok = qi < qn && (row_ids == nullptr || row_ids[qb + qi] >= 0);
+    const typename ScanElem<E>::T* row = src + (qb + (ok ? qi : 0)) * ld;
     const int kbase = chunk * kScanKChunk + 32 * (lane >> 5) + 8 * s;
     uint32_t hb[8], mb[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int k = kbase + j;
-      const float v = (qi < q && k < dim) ? queries[(int64_t)qi * dim + k] : 0.f;
+      const float v = (ok && k < dim) ? scan_elem_f32(E{}, row[k]) : 0.f;
       const uint32_t b = __float_as_uint(v) & 0xffff0000u;
       hb[j] = b >> 16;
       mb[j] = __float_as_uint(v - __uint_as_float(b)) >> 16;
@@ -102,25 +122,31 @@ __global__ __launch_bounds__(kScanThreads) void scan_prep_kernel(const float* __
       mid[d] = mb[2 * d] | (mb[2 * d + 1] << 16);
     }
     out[((0 * 4 + s) * 2 + cb) * 64 + lane] = hi;
-    out[((1 * 4 + s) * 2 + cb) * 64 + lane] = mid;
+    if constexpr (kBTerms == 2) out[((1 * 4 + s) * 2 + cb) * 64 + lane] = mid;
   }
 }
 
-// ||q|| in f32, one wave per query (1 for the padding queries of the last tile); err |= 4 for a query of zero norm
-__global__ __launch_bounds__(kScanThreads) void scan_qnorm_kernel(const float* __restrict__ queries, int q, int qpad, int dim,
-                                                                  float* __restrict__ qnorm, int32_t* __restrict__ err) {
+// ||q|| in f32, one wave per query; 1 for a padding query of the last tile and for a dead row (neither sets an error bit, and
+// nothing reaches the bar the kernels give them); err |= 4 for a live query of zero norm
+template <typename E>
+__global__ __launch_bounds__(kScanThreads) void scan_norm_kernel(const typename ScanElem<E>::T* __restrict__ src, int64_t ld,
+                                                                 int dim, const int64_t* __restrict__ row_ids, int64_t qb, int qn,
+                                                                 int qpad, float* __restrict__ qnorm, int32_t* __restrict__ err) {
   const int lane = threadIdx.x & 63;
   const int qi = blockIdx.x * kScanWaves + (threadIdx.x >> 6);
   if (qi >= qpad) return;
+  const bool ok = qi < qn && (row_ids == nullptr || row_ids[qb + qi] >= 0);
   float ss = 0.f;
-  if (qi < q)
+  if (ok) {
+    const typename ScanElem<E>::T* row = src + (qb + qi) * ld;
     for (int k = lane; k < dim; k += 64) {
-      const float v = queries[(int64_t)qi * dim + k];
+      const float v = scan_elem_f32(E{}, row[k]);
       ss = __builtin_fmaf(v, v, ss);
     }
+  }
   ss = scan_wave_sum(ss);
   if (lane == 0) {
-    const float n = qi < q ? sqrtf(ss) : 1.f;
+    const float n = ok ? sqrtf(ss) : 1.f;
     qnorm[qi] = n;
     if (n == 0.f && err != nullptr) atomicOr(err, 4);
   }
@@ -277,6 +303,17 @@ __device__ __forceinline__ void scan_prune(uint64_t* buf, int cap, int window, u
   else scan_prune_n<4>(buf, n, window, thr, cnt, lane);
 }
 
+// The head of a finished 32-row tile, for all three kernels: nn is this lane's half of its row's ||x||^2 (scan_pass.inc).
+// Returns the row's norm (lane l and lane l ^ 32 hold row l & 31), sets err |= 1 for a live row of zero norm and leaves the
+// live rows as a mask (bit rr = row rr of the tile).
+__device__ __forceinline__ float scan_tile_head(float nn, bool live, int h, int32_t* __restrict__ err, uint32_t& livemask) {
+  nn += __shfl_xor(nn, 32);
+  const float xn = sqrtf(nn);
+  if (live && xn == 0.f && h == 0 && err != nullptr) atomicOr(err, 1);
+  livemask = (uint32_t)__ballot(live);
+  return xn;
+}
+
 // ------------------------------------------------------------------------------------------
 // the scan.  grid (slices, query tiles); dynamic LDS: B chunk | items [64][cap] | threshold [64] | count [64]
 // ------------------------------------------------------------------------------------------
@@ -327,10 +364,8 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
     // the finished 256 x 64 tile: acc[t][cb][i] is row (i & 3) + 8 (i >> 2) + 4 h of tile t, query cb * 32 + r
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      nn[t] += __shfl_xor(nn[t], 32);
-      const float xn = sqrtf(nn[t]);
-      if (live[t] && xn == 0.f && h == 0 && err != nullptr) atomicOr(err, 1);
-      const uint32_t livemask = (uint32_t)__ballot(live[t]);
+      uint32_t livemask;
+      const float xn = scan_tile_head(nn[t], live[t], h, err, livemask);
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) {
         const int qc = cb * 32 + r;
@@ -407,10 +442,60 @@ __device__ __forceinline__ void scan_pass(const typename ScanElem<E>::T* __restr
 }
 
 // ------------------------------------------------------------------------------------------
+// what the two emitting kernels (range scan, self-join) do with a finished 32-row tile
+// ------------------------------------------------------------------------------------------
+// One column block: the dot products acc[i] (row rr = (i & 3) + 8 (i >> 2) + 4 h of the tile, this lane's query) become the
+// approximate scores, in place; returns bit i for a live row whose score reaches `bar` (NaN reaches none) and - GAP, the
+// self-join's diagonal tiles - whose offset in the tile lies beyond `gap`.
+template <bool GAP>
+__device__ __forceinline__ uint32_t scan_mark(f32x16& acc, float xn, float qn, float bar, uint32_t livemask, int h, int gap) {
+  uint32_t hits = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int rr = (i & 3) + 8 * (i >> 2) + 4 * h;
+    const float rn = __shfl(xn, rr);
+    const float sc = acc[i] / (rn * qn);
+    acc[i] = sc;
+    if (((livemask >> rr) & 1u) && (!GAP || rr > gap) && sc >= bar) hits |= 1u << i;
+  }
+  return hits;
+}
+
+// The hits of a wave's tile (bit cb * 16 + i of `hits`) leave through the global cursor: the wave reserves their slots with
+// one 64-bit atomicAdd on `total` (which counts every hit, also those beyond `capacity`: the caller then knows what to
+// allocate) and writes those that fit - first column q0 / q1 (the lane's query of column block 0 / 1), the row, the score.
+template <typename A>
+__device__ __forceinline__ void scan_emit(uint32_t hits, int lane, int h, int64_t capacity, unsigned long long* __restrict__ total,
+                                          A* __restrict__ out_q, A q0, A q1, int64_t* __restrict__ out_row, int64_t row0,
+                                          float* __restrict__ out_approx, const f32x16 (&acc)[2]) {
+  if (__ballot(hits != 0) == 0ull) return;          // (the common case: nothing of this tile reaches a bar)
+  const int mine = __popc(hits);
+  int incl = mine;                      // inclusive prefix sum of the lanes' hit counts
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int v = __shfl_up(incl, off);
+    if (lane >= off) incl += v;
+  }
+  unsigned long long first = 0ull;
+  if (lane == 63) first = atomicAdd(total, (unsigned long long)incl);       // (lane 63's sum is the wave's)
+  int64_t slot = (int64_t)__shfl(first, 63) + (incl - mine);
+#pragma unroll
+  for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (hits & (1u << (cb * 16 + i))) {
+        if (slot < capacity) {
+          out_q[slot] = cb ? q1 : q0;
+          out_row[slot] = row0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+          out_approx[slot] = acc[cb][i];
+        }
+        ++slot;
+      }
+}
+
+// ------------------------------------------------------------------------------------------
 // range scan: the same grid, image and pass; instead of a window per query, EVERY (query, live row) whose approximate score
-// reaches the query's bar goes out.  A wave that has hits in a 32-row tile reserves their slots with one 64-bit atomicAdd on
-// the global cursor `total` (which counts every hit, also those beyond `capacity`: the caller then knows what to allocate) and
-// writes those that fit.  Order unspecified.  LDS: the B chunk only.
+// reaches the query's bar goes out (scan_mark, scan_emit).  Order unspecified.  LDS: the B chunk only.
 // ------------------------------------------------------------------------------------------
 template <typename E, bool ALIGNED>
 __global__ __launch_bounds__(kScanThreads, 2) void scan_above_kernel(const typename ScanElem<E>::T* __restrict__ corpus, int64_t m,
@@ -452,128 +537,29 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_above_kernel(const typen
     // the finished 256 x 64 tile: acc[t][cb][i] is row (i & 3) + 8 (i >> 2) + 4 h of tile t, query cb * 32 + r
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      nn[t] += __shfl_xor(nn[t], 32);
-      const float xn = sqrtf(nn[t]);
-      if (live[t] && xn == 0.f && h == 0 && err != nullptr) atomicOr(err, 1);
-      const uint32_t livemask = (uint32_t)__ballot(live[t]);
+      uint32_t livemask;
+      const float xn = scan_tile_head(nn[t], live[t], h, err, livemask);
       uint32_t hits = 0;                  // bit cb * 16 + i
 #pragma unroll
-      for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int rr = (i & 3) + 8 * (i >> 2) + 4 * h;
-          const float rn = __shfl(xn, rr);
-          const float sc = acc[t][cb][i] / (rn * qn[cb]);
-          acc[t][cb][i] = sc;
-          if (((livemask >> rr) & 1u) && sc >= bar[cb]) hits |= 1u << (cb * 16 + i);
-        }
-      if (__ballot(hits != 0) == 0ull) continue;        // (the common case: nothing of this tile reaches a bar)
-      const int mine = __popc(hits);
-      int incl = mine;                    // inclusive prefix sum of the lanes' hit counts
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-      }
-      unsigned long long first = 0ull;
-      if (lane == 63) first = atomicAdd(total, (unsigned long long)incl);     // (lane 63's sum is the wave's)
-      int64_t slot = (int64_t)__shfl(first, 63) + (incl - mine);
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-          if (hits & (1u << (cb * 16 + i))) {
-            if (slot < capacity) {
-              out_query[slot] = qi[cb];
-              out_row[slot] = row0[t] + (i & 3) + 8 * (i >> 2) + 4 * h;
-              out_approx[slot] = acc[t][cb][i];
-            }
-            ++slot;
-          }
+      for (int cb = 0; cb < 2; ++cb) hits |= scan_mark<false>(acc[t][cb], xn, qn[cb], bar[cb], livemask, h, 0) << (cb * 16);
+      scan_emit(hits, lane, h, capacity, total, out_query, qi[0], qi[1], out_row, row0[t], out_approx, acc[t]);
     }
   }
 }
 
 // ------------------------------------------------------------------------------------------
 // self-join (scan_pairs_kernel, lshrs_scan_pairs_*): the queries are a block [qb, qb + qn) of the stored rows themselves.
-// The image and the norms come straight from the rows - each element converted to f32 exactly, then split and summed as
-// scan_prep_kernel and scan_qnorm_kernel split and sum an f32 query - so an approximate score is the one lshrs_scan_above_*
-// gives the same rows as f32 queries.  A one-term row is exact in bf16: its mid term is zero, the image holds hi only
-// (half the bytes) and the pass issues no MFMA for it (scan_pass.inc, kBTerms = 1).  A dead row, like a padding query, gets a
-// zero image and a norm of 1 and sets no error bit; the pairs kernel gives it a bar of +inf.
+// The image and the norms come straight from the rows, by the kernels that make them of f32 queries (scan_image_kernel,
+// scan_norm_kernel), and a tile is scored and emitted by the range scan's own functions - so an approximate score is the one
+// lshrs_scan_above_* gives the same rows as f32 queries.  The image of one-term rows holds no mid term, and the pass issues
+// no MFMA for it (scan_pass.inc, kBTerms = 1).  A dead row is a padding query to the image and the norms; here it gets a bar
+// of +inf.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float scan_elem_f32(float, float v) { return v; }
-__device__ __forceinline__ float scan_elem_f32(Bf16, uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ float scan_elem_f32(F16, uint16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
-__device__ __forceinline__ float scan_elem_f32(I8, int8_t v) { return (float)v; }
-__device__ __forceinline__ float scan_elem_f32(F8E4M3, uint8_t v) { return __builtin_amdgcn_cvt_f32_fp8((int)v, 0); }
-
-// image: [qtile][chunk][term < kTerms][step s][column block cb][lane] x 16 bytes, the lanes as in scan_prep_kernel
-template <typename E>
-__global__ __launch_bounds__(kScanThreads) void scan_pairs_prep_kernel(const typename ScanElem<E>::T* __restrict__ corpus,
-                                                                       int64_t ldc, int dim, const int64_t* __restrict__ row_ids,
-                                                                       int64_t qb, int qn, int nchunks, u32x4* __restrict__ image) {
-  constexpr int kBTerms = ScanElem<E>::kTerms;
-  const int chunk = blockIdx.x, qtile = blockIdx.y;
-  u32x4* out = image + ((int64_t)qtile * nchunks + chunk) * (kBTerms * 512);
-  for (int f = threadIdx.x; f < 512; f += kScanThreads) {
-    const int lane = f & 63, cb = (f >> 6) & 1, s = f >> 7;
-    const int qi = qtile * kScanQTile + cb * 32 + (lane & 31);
-    const bool ok = qi < qn && (row_ids == nullptr || row_ids[qb + qi] >= 0);
-    const typename ScanElem<E>::T* row = corpus + (qb + (ok ? qi : 0)) * ldc;
-    const int kbase = chunk * kScanKChunk + 32 * (lane >> 5) + 8 * s;
-    uint32_t hb[8], mb[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = kbase + j;
-      const float v = (ok && k < dim) ? scan_elem_f32(E{}, row[k]) : 0.f;
-      const uint32_t b = __float_as_uint(v) & 0xffff0000u;
-      hb[j] = b >> 16;
-      mb[j] = __float_as_uint(v - __uint_as_float(b)) >> 16;
-    }
-    u32x4 hi, mid;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      hi[d] = hb[2 * d] | (hb[2 * d + 1] << 16);
-      mid[d] = mb[2 * d] | (mb[2 * d + 1] << 16);
-    }
-    out[((0 * 4 + s) * 2 + cb) * 64 + lane] = hi;
-    if constexpr (kBTerms == 2) out[((1 * 4 + s) * 2 + cb) * 64 + lane] = mid;
-  }
-}
-
-// ||row|| in f32 in scan_qnorm_kernel's order, one wave per query row of the block (1 for a dead or a padding one); err |= 4
-// for a live row of zero norm
-template <typename E>
-__global__ __launch_bounds__(kScanThreads) void scan_pairs_qnorm_kernel(const typename ScanElem<E>::T* __restrict__ corpus,
-                                                                        int64_t ldc, int dim, const int64_t* __restrict__ row_ids,
-                                                                        int64_t qb, int qn, int qpad, float* __restrict__ qnorm,
-                                                                        int32_t* __restrict__ err) {
-  const int lane = threadIdx.x & 63;
-  const int qi = blockIdx.x * kScanWaves + (threadIdx.x >> 6);
-  if (qi >= qpad) return;
-  const bool ok = qi < qn && (row_ids == nullptr || row_ids[qb + qi] >= 0);
-  float ss = 0.f;
-  if (ok) {
-    const typename ScanElem<E>::T* row = corpus + (qb + qi) * ldc;
-    for (int k = lane; k < dim; k += 64) {
-      const float v = scan_elem_f32(E{}, row[k]);
-      ss = __builtin_fmaf(v, v, ss);
-    }
-  }
-  ss = scan_wave_sum(ss);
-  if (lane == 0) {
-    const float n = ok ? sqrtf(ss) : 1.f;
-    qnorm[qi] = n;
-    if (n == 0.f && err != nullptr) atomicOr(err, 4);
-  }
-}
-
 // One workgroup per CU: at two, this kernel - like scan_above_kernel - fills 256 VGPRs and spills a few loop invariants to
 // scratch; at one the accumulators live in AGPRs and nothing is spilled (self-join).
 constexpr int kScanPairsPerCu = 1;
 
-// grid (slices of the rows [qb, m), query tiles of the block): scan_above_kernel's pass and emitter.  A pair (a, b) goes out
+// grid (slices of the rows [qb, m), query tiles of the block).  A pair (a, b) goes out
 // when a is a live row of the tile, b a live row with b > a (by position: every unordered pair once, no row against itself)
 // and approx >= bar.  The workgroup starts at the pass that holds its tile's first row: no pass whose rows all lie before it.
 template <typename E, bool ALIGNED>
@@ -624,10 +610,8 @@ __global__ __launch_bounds__(kScanThreads, kScanPairsPerCu) void scan_pairs_kern
     // the finished 256 x 64 tile: acc[t][cb][i] is row (i & 3) + 8 (i >> 2) + 4 h of tile t, query row cb * 32 + r of the tile
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      nn[t] += __shfl_xor(nn[t], 32);
-      const float xn = sqrtf(nn[t]);
-      if (live[t] && xn == 0.f && h == 0 && err != nullptr) atomicOr(err, 1);
-      const uint32_t livemask = (uint32_t)__ballot(live[t]);
+      uint32_t livemask;
+      const float xn = scan_tile_head(nn[t], live[t], h, err, livemask);
       uint32_t hits = 0;                  // bit cb * 16 + i
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) {
@@ -636,38 +620,9 @@ __global__ __launch_bounds__(kScanThreads, kScanPairsPerCu) void scan_pairs_kern
         const float bar = ((qlive[cb] >> lane) & 1ull) ? bar_all : __builtin_inff();
         const int64_t ahead = tile_first + cb * 32 - row0[t];          // (uniform)
         const int gap = ahead < -32 ? -1 : ahead > 32 ? 32 : (int)ahead + r;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int rr = (i & 3) + 8 * (i >> 2) + 4 * h;
-          const float rn = __shfl(xn, rr);
-          const float sc = acc[t][cb][i] / (rn * qnv[cb]);
-          acc[t][cb][i] = sc;
-          if (((livemask >> rr) & 1u) && rr > gap && sc >= bar) hits |= 1u << (cb * 16 + i);
-        }
+        hits |= scan_mark<true>(acc[t][cb], xn, qnv[cb], bar, livemask, h, gap) << (cb * 16);
       }
-      if (__ballot(hits != 0) == 0ull) continue;        // (the common case: nothing of this tile reaches the bar)
-      const int mine = __popc(hits);
-      int incl = mine;                    // inclusive prefix sum of the lanes' hit counts
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-      }
-      unsigned long long first = 0ull;
-      if (lane == 63) first = atomicAdd(total, (unsigned long long)incl);     // (lane 63's sum is the wave's)
-      int64_t slot = (int64_t)__shfl(first, 63) + (incl - mine);
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-          if (hits & (1u << (cb * 16 + i))) {
-            if (slot < capacity) {
-              out_a[slot] = tile_first + cb * 32 + r;
-              out_b[slot] = row0[t] + (i & 3) + 8 * (i >> 2) + 4 * h;
-              out_approx[slot] = acc[t][cb][i];
-            }
-            ++slot;
-          }
+      scan_emit(hits, lane, h, capacity, total, out_a, tile_first + r, tile_first + 32 + r, out_b, row0[t], out_approx, acc[t]);
     }
   }
 }
@@ -738,16 +693,28 @@ inline void scan_slices(int64_t m, int qtiles, int64_t lds, int64_t limit, int64
   slices = (int)((m + rps - 1) / rps);
 }
 
-// what the two plans share: the ranges of q, m and dim, and what follows from q and dim alone
-inline int scan_geometry(int32_t q, int64_t m, int32_t dim, ScanPlan& p) {
-  if (q < 0 || m <= 0 || dim <= 0) return LSHRS_E_BADARG;
+// what all three plans share: the ranges of m and dim and the chunks of k ...
+inline int scan_rows_geometry(int64_t m, int32_t dim, ScanPlan& p) {
+  if (m <= 0 || dim <= 0) return LSHRS_E_BADARG;
   if (dim > kScanMaxDim || m > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
-  p.qtiles = (q + kScanQTile - 1) / kScanQTile;
-  if (p.qtiles > 65535) return LSHRS_E_TOOLARGE;
   p.nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
-  p.image_bytes = (int64_t)p.qtiles * p.nchunks * kScanChunkBytes;
-  p.qnorm_bytes = (int64_t)p.qtiles * kScanQTile * (int64_t)sizeof(float);
   return 0;
+}
+
+// ... and the head of the workspace, for `qtiles` tiles of queries: the image (at two terms, whatever the queries hold: the
+// workspace's size knows no element type) and the norms
+inline int scan_front_bytes(int64_t qtiles, ScanPlan& p) {
+  if (qtiles > 65535) return LSHRS_E_TOOLARGE;
+  p.qtiles = (int)qtiles;
+  p.image_bytes = qtiles * p.nchunks * kScanChunkBytes;
+  p.qnorm_bytes = qtiles * kScanQTile * (int64_t)sizeof(float);
+  return 0;
+}
+
+inline int scan_geometry(int32_t q, int64_t m, int32_t dim, ScanPlan& p) {
+  if (q < 0) return LSHRS_E_BADARG;
+  const int bad = scan_rows_geometry(m, dim, p);
+  return bad ? bad : scan_front_bytes((q + kScanQTile - 1) / kScanQTile, p);
 }
 
 inline int scan_plan(int32_t q, int64_t m, int32_t dim, int32_t window, ScanPlan& p) {
@@ -772,28 +739,74 @@ inline int scan_above_plan(int32_t q, int64_t m, int32_t dim, ScanPlan& p) {
   return 0;
 }
 
-// the front of both entries: the image and the query norms at the head of the workspace, written by scan_prep_kernel and
-// scan_qnorm_kernel, and whether the corpus takes the ALIGNED instantiation (16-byte vector loads of whole chunks)
+// self-join: the rows are taken as queries a block at a time.  The plan's block (p.qtiles): 128 query tiles - with the rows in
+// two slices, one round of the 256 workgroups resident at a time, every slice's rows read by 128 of them in step - fewer where
+// the image of that many would pass 256 MiB or the rows end.  A caller's block (a multiple of 64) is taken as it is.  The
+// slices are each block's own (scan_pairs).
+constexpr int kScanPairsBlock = 8192;
+constexpr int64_t kScanPairsImageBytes = 256ll << 20;
+
+inline int scan_pairs_plan(int64_t m, int32_t dim, int32_t qblock, ScanPlan& p) {
+  if (qblock < 0 || qblock % kScanQTile) return LSHRS_E_BADARG;
+  const int bad = scan_rows_geometry(m, dim, p);
+  if (bad) return bad;
+  int64_t tiles = qblock / kScanQTile;
+  if (qblock == 0) {
+    const int64_t tile_bytes = (int64_t)p.nchunks * kScanChunkBytes;
+    tiles = kScanPairsBlock / kScanQTile;
+    if (tiles > kScanPairsImageBytes / tile_bytes) tiles = kScanPairsImageBytes / tile_bytes;     // (at least 64: 4 MiB a tile)
+    if (tiles > (m + kScanQTile - 1) / kScanQTile) tiles = (m + kScanQTile - 1) / kScanQTile;
+  }
+  p.cap = p.slices = 0;
+  p.rows_per_slice = p.parts_bytes = 0;
+  return scan_front_bytes(tiles, p);
+}
+
+// the front of all three entries: the image and the norms at the head of the workspace, written by scan_image_kernel and
+// scan_norm_kernel from `qn` queries - rows of Q at `qsrc` (stride qld), those from qb on, the dead ones by `qrow_ids` left
+// out: f32 queries, or a block of the corpus itself - and whether the corpus takes the ALIGNED instantiation (16-byte vector
+// loads of whole chunks).  p.qtiles covers qn; p.image_bytes may be a larger block's.
 struct ScanFront {
   u32x4* image;
   float* qnorm;
   bool aligned;
 };
 
-template <typename E>
-ScanFront scan_front(const ScanPlan& p, const typename ScanElem<E>::T* corpus, int64_t ldc, int32_t dim, const float* queries,
-                     int32_t q, void* workspace, int32_t* err, hipStream_t s) {
+template <typename E, typename Q>
+ScanFront scan_front(const ScanPlan& p, const typename ScanElem<E>::T* corpus, int64_t ldc, int32_t dim,
+                     const typename ScanElem<Q>::T* qsrc, int64_t qld, const int64_t* qrow_ids, int64_t qb, int32_t qn,
+                     void* workspace, int32_t* err, hipStream_t s) {
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   ScanFront f;
   f.image = reinterpret_cast<u32x4*>(ws);
   f.qnorm = reinterpret_cast<float*>(ws + p.image_bytes);
   f.aligned = (ldc % ScanElem<E>::kAlign == 0) && ((reinterpret_cast<uintptr_t>(corpus) & 15) == 0);
   const int qpad = p.qtiles * kScanQTile;
-  hipLaunchKernelGGL(scan_prep_kernel, dim3((unsigned)p.nchunks, (unsigned)p.qtiles), dim3(kScanThreads), 0, s, queries, q, dim,
-                     p.nchunks, f.image);
-  hipLaunchKernelGGL(scan_qnorm_kernel, dim3((unsigned)(qpad / kScanWaves)), dim3(kScanThreads), 0, s, queries, q, qpad, dim,
-                     f.qnorm, err);
+  hipLaunchKernelGGL((scan_image_kernel<Q>), dim3((unsigned)p.nchunks, (unsigned)p.qtiles), dim3(kScanThreads), 0, s, qsrc, qld,
+                     dim, qrow_ids, qb, qn, p.nchunks, f.image);
+  hipLaunchKernelGGL((scan_norm_kernel<Q>), dim3((unsigned)(qpad / kScanWaves)), dim3(kScanThreads), 0, s, qsrc, qld, dim,
+                     qrow_ids, qb, qn, qpad, f.qnorm, err);
   return f;
+}
+
+// ... with f32 queries (q, dim), all of them
+template <typename E>
+ScanFront scan_front(const ScanPlan& p, const typename ScanElem<E>::T* corpus, int64_t ldc, int32_t dim, const float* queries,
+                     int32_t q, void* workspace, int32_t* err, hipStream_t s) {
+  return scan_front<E, float>(p, corpus, ldc, dim, queries, dim, nullptr, 0, q, workspace, err, s);
+}
+
+// what the two emitting entries check alike, then the cursor's reset: the last thing before the launches
+template <typename A>
+int scan_emit_begin(const void* corpus, int64_t ldc, int32_t dim, int64_t capacity, const A* out_first, const int64_t* out_row,
+                    const float* out_approx, uint64_t* total, const void* workspace, hipStream_t s) {
+  const auto addr = [](const void* ptr) { return reinterpret_cast<uintptr_t>(ptr); };
+  if (corpus == nullptr || total == nullptr || workspace == nullptr || capacity < 0 ||
+      (capacity > 0 && (out_first == nullptr || out_row == nullptr || out_approx == nullptr)) || (addr(workspace) & 15) ||
+      (addr(total) & 7) || (addr(out_first) & (sizeof(A) - 1)) || (addr(out_row) & 7) || (addr(out_approx) & 3) || ldc < dim)
+    return LSHRS_E_BADARG;
+  const hipError_t e = hipMemsetAsync(total, 0, sizeof(uint64_t), s);
+  return e != hipSuccess ? -(int)e : 0;
 }
 
 template <typename E, bool ALIGNED>
@@ -850,15 +863,11 @@ int scan_above(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, in
   ScanPlan p;
   const int bad = scan_above_plan(q, m, dim, p);
   if (bad) return bad;
-  const auto addr = [](const void* ptr) { return reinterpret_cast<uintptr_t>(ptr); };
-  if (corpus == nullptr || queries == nullptr || bars == nullptr || total == nullptr || workspace == nullptr || capacity < 0 ||
-      (capacity > 0 && (out_query == nullptr || out_row == nullptr || out_approx == nullptr)) || (addr(workspace) & 15) ||
-      (addr(total) & 7) || (addr(out_row) & 7) || (addr(out_query) & 3) || (addr(out_approx) & 3) || (addr(bars) & 3) ||
-      (addr(queries) & 3) || ldc < dim)
+  if (queries == nullptr || bars == nullptr || (reinterpret_cast<uintptr_t>(bars) & 3) || (reinterpret_cast<uintptr_t>(queries) & 3))
     return LSHRS_E_BADARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const hipError_t e = hipMemsetAsync(total, 0, sizeof(uint64_t), s);
-  if (e != hipSuccess) return -(int)e;
+  const int rc = scan_emit_begin(corpus, ldc, dim, capacity, out_query, out_row, out_approx, total, workspace, s);
+  if (rc) return rc;
   const ScanFront f = scan_front<E>(p, corpus, ldc, dim, queries, q, workspace, err, s);
   const dim3 grid((unsigned)p.slices, (unsigned)p.qtiles), block(kScanThreads);
   unsigned long long* cursor = reinterpret_cast<unsigned long long*>(total);
@@ -871,77 +880,33 @@ int scan_above(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, in
   return -(int)hipGetLastError();
 }
 
-// self-join: the rows are taken as queries a block at a time.  The plan's block: 128 query tiles - with the rows in two
-// slices, one round of the 256 workgroups resident at a time, every slice's rows read by 128 of them in step - fewer where the
-// image of that many (at two terms, whatever the rows hold: the workspace's size knows no element type) would pass 256 MiB or
-// the rows end.  A caller's block (a multiple of 64) is taken as it is.
-constexpr int kScanPairsBlock = 8192;
-constexpr int64_t kScanPairsImageBytes = 256ll << 20;
-
-struct ScanPairsPlan {
-  int qblock, nchunks;
-  int64_t image_bytes, qnorm_bytes;
-};
-
-inline int scan_pairs_plan(int64_t m, int32_t dim, int32_t qblock, ScanPairsPlan& p) {
-  if (m <= 0 || dim <= 0 || qblock < 0 || qblock % kScanQTile) return LSHRS_E_BADARG;
-  if (dim > kScanMaxDim || m > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
-  p.nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
-  const int64_t tile_bytes = (int64_t)p.nchunks * kScanChunkBytes;
-  int64_t tiles = qblock / kScanQTile;
-  if (qblock == 0) {
-    tiles = kScanPairsBlock / kScanQTile;
-    if (tiles > kScanPairsImageBytes / tile_bytes) tiles = kScanPairsImageBytes / tile_bytes;     // (at least 64: 4 MiB a tile)
-    if (tiles > (m + kScanQTile - 1) / kScanQTile) tiles = (m + kScanQTile - 1) / kScanQTile;
-  }
-  if (tiles > 65535) return LSHRS_E_TOOLARGE;
-  p.qblock = (int)tiles * kScanQTile;
-  p.image_bytes = tiles * tile_bytes;
-  p.qnorm_bytes = tiles * kScanQTile * (int64_t)sizeof(float);
-  return 0;
-}
-
 template <typename E>
 int scan_pairs(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, float bar,
                int32_t qblock, int64_t capacity, int64_t* out_a, int64_t* out_b, float* out_approx, uint64_t* total,
                void* workspace, int32_t* err, void* stream) {
-  constexpr int kBTerms = ScanElem<E>::kTerms;
-  ScanPairsPlan p;
+  ScanPlan p;
   const int bad = scan_pairs_plan(m, dim, qblock, p);
   if (bad) return bad;
-  const auto addr = [](const void* ptr) { return reinterpret_cast<uintptr_t>(ptr); };
-  if (corpus == nullptr || total == nullptr || workspace == nullptr || capacity < 0 ||
-      (capacity > 0 && (out_a == nullptr || out_b == nullptr || out_approx == nullptr)) || (addr(workspace) & 15) ||
-      (addr(total) & 7) || (addr(out_a) & 7) || (addr(out_b) & 7) || (addr(out_approx) & 3) || (addr(row_ids) & 7) || ldc < dim)
-    return LSHRS_E_BADARG;
+  if (reinterpret_cast<uintptr_t>(row_ids) & 7) return LSHRS_E_BADARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const hipError_t e = hipMemsetAsync(total, 0, sizeof(uint64_t), s);
-  if (e != hipSuccess) return -(int)e;
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  u32x4* image = reinterpret_cast<u32x4*>(ws);
-  float* qnorm = reinterpret_cast<float*>(ws + p.image_bytes);
-  const bool aligned = (ldc % ScanElem<E>::kAlign == 0) && ((addr(corpus) & 15) == 0);
+  const int rc = scan_emit_begin(corpus, ldc, dim, capacity, out_a, out_b, out_approx, total, workspace, s);
+  if (rc) return rc;
   unsigned long long* cursor = reinterpret_cast<unsigned long long*>(total);
-  const size_t lds = (size_t)kBTerms * (kScanChunkBytes / 2);
-  const dim3 block(kScanThreads);
+  const size_t lds = (size_t)ScanElem<E>::kTerms * (kScanChunkBytes / 2);
+  const int64_t block_rows = (int64_t)p.qtiles * kScanQTile;
   // the blocks one after the other on the stream: they share the image, the norms and the cursor
-  for (int64_t qb = 0; qb < m; qb += p.qblock) {
-    const int qn = (int)(m - qb < p.qblock ? m - qb : p.qblock);
-    const int qtiles = (qn + kScanQTile - 1) / kScanQTile, qpad = qtiles * kScanQTile;
-    int64_t rows_per_slice;
-    int slices;
-    scan_slices(m - qb, qtiles, (int64_t)lds, INT64_MAX, rows_per_slice, slices, kScanPairsPerCu);
-    hipLaunchKernelGGL((scan_pairs_prep_kernel<E>), dim3((unsigned)p.nchunks, (unsigned)qtiles), block, 0, s, corpus, ldc, dim,
-                       row_ids, qb, qn, p.nchunks, image);
-    hipLaunchKernelGGL((scan_pairs_qnorm_kernel<E>), dim3((unsigned)(qpad / kScanWaves)), block, 0, s, corpus, ldc, dim, row_ids,
-                       qb, qn, qpad, qnorm, err);
-    const dim3 grid((unsigned)slices, (unsigned)qtiles);
-    if (aligned)
-      hipLaunchKernelGGL((scan_pairs_kernel<E, true>), grid, block, lds, s, corpus, m, ldc, dim, row_ids, image, qnorm, bar, qb,
-                         qn, rows_per_slice, capacity, out_a, out_b, out_approx, cursor, err);
+  for (int64_t qb = 0; qb < m; qb += block_rows) {
+    const int qn = (int)(m - qb < block_rows ? m - qb : block_rows);
+    p.qtiles = (qn + kScanQTile - 1) / kScanQTile;
+    scan_slices(m - qb, p.qtiles, (int64_t)lds, INT64_MAX, p.rows_per_slice, p.slices, kScanPairsPerCu);
+    const ScanFront f = scan_front<E, E>(p, corpus, ldc, dim, corpus, ldc, row_ids, qb, qn, workspace, err, s);
+    const dim3 grid((unsigned)p.slices, (unsigned)p.qtiles), block(kScanThreads);
+    if (f.aligned)
+      hipLaunchKernelGGL((scan_pairs_kernel<E, true>), grid, block, lds, s, corpus, m, ldc, dim, row_ids, f.image, f.qnorm, bar,
+                         qb, qn, p.rows_per_slice, capacity, out_a, out_b, out_approx, cursor, err);
     else
-      hipLaunchKernelGGL((scan_pairs_kernel<E, false>), grid, block, lds, s, corpus, m, ldc, dim, row_ids, image, qnorm, bar, qb,
-                         qn, rows_per_slice, capacity, out_a, out_b, out_approx, cursor, err);
+      hipLaunchKernelGGL((scan_pairs_kernel<E, false>), grid, block, lds, s, corpus, m, ldc, dim, row_ids, f.image, f.qnorm, bar,
+                         qb, qn, p.rows_per_slice, capacity, out_a, out_b, out_approx, cursor, err);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) return -(int)le;
   }
@@ -1044,7 +1009,7 @@ int lshrs_scan_above_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32
 }
 
 int64_t lshrs_scan_pairs_workspace_bytes(int64_t m, int32_t dim, int32_t qblock) {
-  ScanPairsPlan p;
+  ScanPlan p;
   const int bad = scan_pairs_plan(m, dim, qblock, p);
   if (bad) return bad;
   return p.image_bytes + p.qnorm_bytes + 16;

@@ -498,6 +498,25 @@ def test_edges():
         exact_above(Q, xd, [0.5, 0.5])
 
 
+def test_negative_zero_ties_with_zero():
+    """Equal scores go by ascending id, and -0.0 equals 0.0.  Row 0 scores -0.0 (a dot product of -1e-30 over norms of 1e10
+    each: the quotient underflows), row 1 scores 0.0, row 2 is the query: the answer is [2, 0, 1] - an order by the scores' bits
+    would put row 1 before row 0.  The same through the self-join's ordering: the pairs (0, 1) at -0.0 and (0, 2) at 0.0."""
+    torch = _torch()
+    from lshrs_amd import exact_above, exact_pairs_above
+
+    q = np.array([[1e-15, 1e10, 0.0, 0.0]], dtype=np.float32)
+    rows = np.array([[-1e-15, 0.0, 1e10, 0.0], [0.0, 0.0, 1e10, 0.0], [1e-15, 1e10, 0.0, 0.0]], dtype=np.float32)
+    ids, scores, bounds = exact_above(q, torch.from_numpy(rows).cuda(), -0.5)
+    assert bounds.tolist() == [0, 3] and scores[0] > 0.9
+    assert scores[1:].tolist() == [0.0, 0.0] and np.signbit(scores[1:]).tolist() == [True, False], scores
+    assert ids.tolist() == [2, 0, 1]
+    pair_rows = np.array([[1e-15, 1e10, 0.0, 0.0], [-1e-15, 0.0, 1e10, 0.0], [0.0, 0.0, 0.0, 1e10]], dtype=np.float32)
+    ia, ib, ps = exact_pairs_above(torch.from_numpy(pair_rows).cuda(), -0.5)
+    assert ps.tolist() == [0.0, 0.0, 0.0] and np.signbit(ps).tolist() == [True, False, False], ps
+    assert list(zip(ia.tolist(), ib.tolist())) == [(0, 1), (0, 2), (1, 2)]
+
+
 def test_rows_longer_than_the_kernels_take_raise_what_the_rerank_raises():
     torch = _torch()
     from lshrs_amd import NativeLibraryError, exact_above, rerank_batch

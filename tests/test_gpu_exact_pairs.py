@@ -176,6 +176,23 @@ def test_first_pass_on_rows_at_any_address_and_stride(name):
         _check_first_pass(view, c["ids"], A, live, qblock, f"unaligned {name}, qblock {qblock}")
 
 
+@pytest.mark.parametrize("name", ("float32", "bfloat16"))
+def test_first_pass_takes_nothing_from_behind_a_rows_last_element(name):
+    """Rows of 70 elements at a stride of 128 (one whole chunk of 64 and a part of the next; 300 rows: one whole pass and a part
+    of the next; blocks of 64: diagonal tiles and tiles off it), NaN in the 58 places behind each row.  The image of the query
+    rows is zero beyond dim whatever the memory holds there: one NaN in it would make every score of its row NaN (0 * NaN), and
+    no pair of that row would reach even a bar of -inf.  A two-term type and a one-term one."""
+    torch = _torch()
+    m, dim, ld = 300, 70, 128
+    c = _case(m, dim, name, "dead")
+    A, live = _approx(m, dim, name, "dead")
+    flat = torch.full((m, ld), float("nan"), dtype=c["stored"].dtype, device="cuda")
+    view = flat[:, :dim]
+    view.copy_(c["stored"])
+    assert view.stride(0) == ld and bool(torch.isnan(flat[:, dim:].float()).all())
+    _check_first_pass(view, c["ids"], A, live, 64, f"NaN behind the rows, {name}")
+
+
 def test_first_pass_with_a_bar():
     """A finite bar: exactly the pairs whose approximate score reaches it."""
     from lshrs_amd._exact import scan_pairs
