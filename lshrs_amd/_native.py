@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
 import threading
 from typing import Optional
@@ -23,6 +24,7 @@ SOURCE = SOURCES[0]
 # (LSHRS_HIP_LIBRARY: load another build of the same ABI instead - A/B measurements of compiler flags, tools/ab_build.py)
 LIBRARY = os.environ.get("LSHRS_HIP_LIBRARY") or os.path.join(CSRC, "liblshrs_hip.so")
 INCLUDE = os.path.join(REPO_ROOT, "include")
+HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility-inlines-hidden")   # of every unit's compilation
 ABI_VERSION = 7
 QUERY_MAX_PAIRS = 16384   # LSHRS_QUERY_MAX_PAIRS
 SIG_COUNTERS = 8          # LSHRS_SIG_COUNTERS of include/lshrs_hip.h
@@ -46,6 +48,21 @@ class NativeLibraryError(RuntimeError):
     """The HIP extension is missing, stale or reported an error."""
 
 
+def _sources_of(path: str, seen: Optional[set] = None) -> set:
+    """A unit and the project's files it #includes, directly or through one of them: every quoted name that exists under
+    csrc/ or include/ (headers and *.inc texts alike - no list to keep)."""
+    seen = {path} if seen is None else seen
+    with open(path, encoding="utf-8") as fh:
+        names = re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', fh.read(), re.M)
+    for name in names:
+        for folder in (CSRC, INCLUDE):
+            dep = os.path.join(folder, name)
+            if os.path.exists(dep) and dep not in seen:
+                seen.add(dep)
+                _sources_of(dep, seen)
+    return seen
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP sources for gfx950 into the in-tree shared library (and the host tie-break engine).
     One object per translation unit (kernels + C ABI, native pipeline driver), rebuilt only when stale."""
@@ -53,8 +70,6 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
     _hostblas.build(force=force, verbose=verbose)
     with _lock:
-        header = max(os.path.getmtime(p) for p in (os.path.join(INCLUDE, "lshrs_hip.h"), os.path.join(CSRC, "lshrs_common.h"),
-                                                   os.path.join(CSRC, "scan_pass.inc")))
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         objdir = os.path.join(CSRC, "_obj")
         os.makedirs(objdir, exist_ok=True)
@@ -62,13 +77,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
         for src in SOURCES:
             obj = os.path.join(objdir, os.path.basename(src) + ".o")
             objects.append(obj)
-            if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), header):
+            if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(p) for p in _sources_of(src)):
                 stale.append((src, obj))
 
         def compile_one(job):
             src, obj = job
-            cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility-inlines-hidden", "-I" + INCLUDE,
-                   "-I" + CSRC, "-c", src, "-o", obj + ".tmp"]
+            cmd = [hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-I" + CSRC, "-c", src, "-o", obj + ".tmp"]
             if verbose:
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)

@@ -6,8 +6,10 @@
 // 64-bit items; the lists are a few hundred to a few thousand entries: they never go through global memory), the
 // per-query order by score, and the compaction of what the caller asked for.  Integer / index work: bit-exact by
 // construction; HBM traffic is the bucket members once and the candidates once.
+// The order by score (desc_item: descending key above the position) and the LDS network's pass (bitonic_pass.inc) are the
+// rerank's own: lshrs_rows.h.
 // ABI and reference citations: include/lshrs_hip.h.  Design notes: DESIGN.md §10.
-#include "lshrs_common.h"
+#include "lshrs_rows.h"
 
 using namespace lshrs;
 
@@ -94,21 +96,12 @@ __device__ __forceinline__ void bitonic_sort_lds(uint64_t* items, int P) {
   if (P <= 2 * kQThreads) return bitonic_sort_regs<2>(items, P);
 #endif
   __syncthreads();
-  for (int size = 2; size <= P; size <<= 1) {
+  constexpr int kPassThreads = kQThreads, base = 0;
+  const int n = P;
+  for (int size = 2; size <= P; size <<= 1)
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < (P >> 1); t += kQThreads) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool up = ((lo & size) == 0);
-        const uint64_t a = items[lo], b = items[hi];
-        if ((a > b) == up) {
-          items[lo] = b;
-          items[hi] = a;
-        }
-      }
-      __syncthreads();
+#include "bitonic_pass.inc"
     }
-  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -451,15 +444,8 @@ __global__ __launch_bounds__(kQThreads) void query_one_kernel(const uint8_t* __r
 // Per query: the candidates in descending score (ties by ascending candidate position, NaN last - as lshrs_topk_desc_f32),
 // the first keep[q] of them written to the caller's compact result arrays.  scores == NULL: the order the candidates
 // already have (collision order: the top_k-by-collisions answer of LSHRS.query, main.py:619-625).
-// (+0.0 ranks ahead of -0.0 wherever they stand: the key is the sign-magnitude order of the bits.)
+// (+0.0 ranks ahead of -0.0 wherever they stand: the key is the sign-magnitude order of the bits - desc_key, lshrs_rows.h.)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t desc_key(float f) {
-  if (f != f) return 0xFFFFFFFFu;
-  uint32_t u = __float_as_uint(f);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~u;
-}
-
 __global__ __launch_bounds__(kQThreads) void query_rank_kernel(const int64_t* __restrict__ cand_ids,
                                                                const float* __restrict__ scores,
                                                                const int64_t* __restrict__ pair_off,
@@ -481,7 +467,7 @@ __global__ __launch_bounds__(kQThreads) void query_rank_kernel(const int64_t* __
       const int U = ucount[qi];
       const int P = pow2_ceil(U);
       for (int t = tid; t < P; t += kQThreads)
-        items[t] = t < U ? (((uint64_t)desc_key(scores[base + t]) << 32) | (uint32_t)t) : ~0ull;
+        items[t] = t < U ? desc_item(scores[base + t], (uint32_t)t) : ~0ull;
       bitonic_sort_lds(items, P);
       for (int t = tid; t < K; t += kQThreads) {
         const uint32_t pos = (uint32_t)items[t];

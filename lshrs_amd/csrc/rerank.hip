@@ -1,10 +1,14 @@
 // rerank.hip - part of liblshrs_hip.so, the gfx950 (MI355X / CDNA4) implementation of the lshrs hot path.
 // K2 cosine of gathered candidates (gather + dot + norm), L2 normalisation, K3 per-query descending order (LDS bitonic
 // network; longer lists through global memory).
-// One translation unit per kernel family (round 5): what is shared lives in lshrs_common.h, measurement switches (-DLSHRS_AB_*,
-// tools/ab_build.py) are local to the unit whose kernel they alter and reported through lshrs_build_flags().
+// One translation unit per kernel family (round 5): what is shared lives in lshrs_common.h and - the element types of a stored
+// row and their exact conversions, the wave's sum, the orderable key of a score and the networks' item: shared with scan.hip
+// and query.hip - in lshrs_rows.h; measurement switches (-DLSHRS_AB_*, tools/ab_build.py) are local to the unit whose kernel
+// they alter and reported through lshrs_build_flags().
+// Two layers are texts #included where they run (each says why it is no function): cos_finish.inc, the end of a candidate;
+// bitonic_pass.inc, one pass of the LDS network (also query.hip's).
 // ABI and reference citations: include/lshrs_hip.h.  Design notes: DESIGN.md.
-#include "lshrs_common.h"
+#include "lshrs_rows.h"
 
 #include <type_traits>
 
@@ -29,63 +33,12 @@ constexpr int kCosThreads = 256;
 constexpr int kCosWaves = kCosThreads / 64;
 constexpr int kCosInflight = 4;
 
-struct Bf16 {};   // element tags of a 16-bit corpus (rows of uint16_t)
-struct F16 {};
-struct I8 {};     // element tags of an 8-bit corpus (rows of int8_t / uint8_t)
-struct F8E4M3 {};
-
-// per element type: what a row holds, rows in flight per wave, elements per 16-B load
+// per element type (lshrs_rows.h: the tags, RowT<E>, the conversions): rows in flight per wave, elements per 16-B load
 template <typename E> struct CosElem {
-  using T = uint16_t;
-  static constexpr int kInflight = 2 * kCosInflight;
-  static constexpr int kVec = 8;
+  using T = RowT<E>;
+  static constexpr int kVec = 4 * kRowPerDword<E>;
+  static constexpr int kInflight = kRowPerDword<E> * kCosInflight;
 };
-template <> struct CosElem<float> {
-  using T = float;
-  static constexpr int kInflight = kCosInflight;
-  static constexpr int kVec = 4;
-};
-template <> struct CosElem<I8> {
-  using T = int8_t;
-  static constexpr int kInflight = 4 * kCosInflight;
-  static constexpr int kVec = 16;
-};
-template <> struct CosElem<F8E4M3> {
-  using T = uint8_t;
-  static constexpr int kInflight = 4 * kCosInflight;
-  static constexpr int kVec = 16;
-};
-
-// exact conversions: the element in the low / high half of a dword, and a lone 16-bit element
-__device__ __forceinline__ float elem_lo(Bf16, uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float elem_hi(Bf16, uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ float elem_lo(F16, uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)w); }
-__device__ __forceinline__ float elem_hi(F16, uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
-template <typename E>
-__device__ __forceinline__ float elem(uint16_t bits) { return elem_lo(E{}, bits); }
-
-// exact conversions of 8-bit elements: the four bytes of a dword (in memory order), and a lone byte.  e4m3fn goes through
-// gfx950's fp8 conversion, which reads the OCP encoding (not MI300's fnuz): subnormals kept, 0x7f / 0xff -> NaN.
-__device__ __forceinline__ void elem4(I8, uint32_t w, float (&x)[4]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) x[j] = (float)(int8_t)(w >> (8 * j));
-}
-__device__ __forceinline__ void elem4(F8E4M3, uint32_t w, float (&x)[4]) {
-  // (one conversion per byte, like int8's: each result feeds a packed FMA as it is - the pairwise conversion's pairs would
-  // have to be taken apart first)
-  x[0] = __builtin_amdgcn_cvt_f32_fp8((int)w, 0);
-  x[1] = __builtin_amdgcn_cvt_f32_fp8((int)w, 1);
-  x[2] = __builtin_amdgcn_cvt_f32_fp8((int)w, 2);
-  x[3] = __builtin_amdgcn_cvt_f32_fp8((int)w, 3);
-}
-__device__ __forceinline__ float elem1(I8, int8_t b) { return (float)b; }
-__device__ __forceinline__ float elem1(F8E4M3, uint8_t b) { return __builtin_amdgcn_cvt_f32_fp8((int)b, 0); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // RAGGED (ABI 7, lshrs_cosine_ragged_f32): query qi has row_cnt[qi] candidates, listed - and scored - at row_off[qi] of the
 // flat cand_idx / scores arrays (the candidate lists of a batch of LSH queries, lshrs/core/main.py:629-646); what is wrong with
@@ -159,104 +112,43 @@ __global__ __launch_bounds__(kCosThreads) void cosine_kernel(const typename CosE
 #pragma unroll
     for (int u = 0; u < kInflight; ++u) { dot[u] = 0.f; nn[u] = 0.f; }
 
-    if constexpr (std::is_same_v<E, float>) {
-      if (ALIGNED) {
-        for (int k = lane * 4; k < dim; k += 256) {
-          const f32x4 qx = *reinterpret_cast<const f32x4*>(qlds + k);
-          f32x4 cx[kInflight];
+    // elements of a dword in memory order, dwords in order: the same sums per lane for every type
+    constexpr int kPer = kRowPerDword<E>, kVec = CosElem<E>::kVec;
+    if (ALIGNED) {
+      // kVec elements per lane per load (dim, ldc multiples of kVec, 16-B aligned base): one 16-B load of the row
+      for (int k = lane * kVec; k < dim; k += 64 * kVec) {
+        float qx[kVec];
 #pragma unroll
-          for (int u = 0; u < kInflight; ++u) cx[u] = *reinterpret_cast<const f32x4*>(rowp[u] + k);
+        for (int v = 0; v < kPer; ++v) {
+          const f32x4 qv4 = *reinterpret_cast<const f32x4*>(qlds + k + 4 * v);
 #pragma unroll
-          for (int u = 0; u < kInflight; ++u)
+          for (int e = 0; e < 4; ++e) qx[4 * v + e] = qv4[e];
+        }
+        u32x4 cx[kInflight];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              dot[u] = __builtin_fmaf(cx[u][e], qx[e], dot[u]);
-              nn[u] = __builtin_fmaf(cx[u][e], cx[u][e], nn[u]);
+        for (int u = 0; u < kInflight; ++u) cx[u] = *reinterpret_cast<const u32x4*>(rowp[u] + k);
+#pragma unroll
+        for (int u = 0; u < kInflight; ++u)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float x[kPer];
+            row_unpack(E{}, cx[u][e], x);
+#pragma unroll
+            for (int j = 0; j < kPer; ++j) {
+              dot[u] = __builtin_fmaf(x[j], qx[kPer * e + j], dot[u]);
+              nn[u] = __builtin_fmaf(x[j], x[j], nn[u]);
             }
-        }
-      } else {
-        for (int k = lane; k < dim; k += 64) {
-          const float qx = qlds[k];
-#pragma unroll
-          for (int u = 0; u < kInflight; ++u) {
-            const float cx = rowp[u][k];
-            dot[u] = __builtin_fmaf(cx, qx, dot[u]);
-            nn[u] = __builtin_fmaf(cx, cx, nn[u]);
           }
-        }
-      }
-    } else if constexpr (sizeof(T) == 1) {
-      if (ALIGNED) {
-        // 16 elements per lane per load (dim, ldc multiples of 16, 16-B aligned base): elements 4e .. 4e+3 of the 16 are the
-        // bytes of dword e, summed in element order
-        for (int k = lane * 16; k < dim; k += 1024) {
-          float qx[16];
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const f32x4 qv4 = *reinterpret_cast<const f32x4*>(qlds + k + 4 * v);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) qx[4 * v + e] = qv4[e];
-          }
-          u32x4 cx[kInflight];
-#pragma unroll
-          for (int u = 0; u < kInflight; ++u) cx[u] = *reinterpret_cast<const u32x4*>(rowp[u] + k);
-#pragma unroll
-          for (int u = 0; u < kInflight; ++u)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              float x[4];
-              elem4(E{}, cx[u][e], x);
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                dot[u] = __builtin_fmaf(x[j], qx[4 * e + j], dot[u]);
-                nn[u] = __builtin_fmaf(x[j], x[j], nn[u]);
-              }
-            }
-        }
-      } else {
-        // any dim, row stride and byte address: one element per lane per load
-        for (int k = lane; k < dim; k += 64) {
-          const float qx = qlds[k];
-#pragma unroll
-          for (int u = 0; u < kInflight; ++u) {
-            const float cx = elem1(E{}, rowp[u][k]);
-            dot[u] = __builtin_fmaf(cx, qx, dot[u]);
-            nn[u] = __builtin_fmaf(cx, cx, nn[u]);
-          }
-        }
       }
     } else {
-      if (ALIGNED) {
-        // 8 elements per lane per load (dim, ldc multiples of 8, 16-B aligned base): element 2e / 2e+1 of the 8 are the
-        // low / high half of dword e, summed in element order
-        for (int k = lane * 8; k < dim; k += 512) {
-          const f32x4 q0 = *reinterpret_cast<const f32x4*>(qlds + k);
-          const f32x4 q1 = *reinterpret_cast<const f32x4*>(qlds + k + 4);
-          const float qx[8] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
-          u32x4 cx[kInflight];
+      // any dim, row stride and address: one element per lane per load
+      for (int k = lane; k < dim; k += 64) {
+        const float qx = qlds[k];
 #pragma unroll
-          for (int u = 0; u < kInflight; ++u) cx[u] = *reinterpret_cast<const u32x4*>(rowp[u] + k);
-#pragma unroll
-          for (int u = 0; u < kInflight; ++u)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float a = elem_lo(E{}, cx[u][e]), b = elem_hi(E{}, cx[u][e]);
-              dot[u] = __builtin_fmaf(a, qx[2 * e], dot[u]);
-              nn[u] = __builtin_fmaf(a, a, nn[u]);
-              dot[u] = __builtin_fmaf(b, qx[2 * e + 1], dot[u]);
-              nn[u] = __builtin_fmaf(b, b, nn[u]);
-            }
-        }
-      } else {
-        // any dim and row stride: one element per lane per load
-        for (int k = lane; k < dim; k += 64) {
-          const float qx = qlds[k];
-#pragma unroll
-          for (int u = 0; u < kInflight; ++u) {
-            const float cx = elem<E>(rowp[u][k]);
-            dot[u] = __builtin_fmaf(cx, qx, dot[u]);
-            nn[u] = __builtin_fmaf(cx, cx, nn[u]);
-          }
+        for (int u = 0; u < kInflight; ++u) {
+          const float cx = row_elem_f32(E{}, rowp[u][k]);
+          dot[u] = __builtin_fmaf(cx, qx, dot[u]);
+          nn[u] = __builtin_fmaf(cx, cx, nn[u]);
         }
       }
     }
@@ -288,16 +180,7 @@ __global__ __launch_bounds__(kCosThreads) void cosine_kernel(const typename CosE
       for (int u = 0; u < kInflight; ++u) code = (u == ur) ? st[u] : code;
       if ((lane & 33) == 0 && code != 3) {
         const int64_t o = obase + base + ur;
-        float sc;
-        if (code == 0) {
-          const float cn = sqrtf(s2);
-          if (cn == 0.f) code = 1;
-          sc = d / (cn * qnorm);
-        }
-        if (code != 0) sc = __builtin_nanf("");
-        scores[o] = sc;
-        if (status != nullptr) status[o] = (uint8_t)code;
-        if (RAGGED && code != 0 && err != nullptr) atomicOr(err, code);
+#include "cos_finish.inc"
       }
       continue;
     }
@@ -308,16 +191,7 @@ __global__ __launch_bounds__(kCosThreads) void cosine_kernel(const typename CosE
       if (lane == 0 && st[u] != 3) {
         const int64_t o = obase + base + u;
         int code = st[u];
-        float sc;
-        if (code == 0) {
-          const float cn = sqrtf(s2);
-          if (cn == 0.f) code = 1;
-          sc = d / (cn * qnorm);
-        }
-        if (code != 0) sc = __builtin_nanf("");
-        scores[o] = sc;
-        if (status != nullptr) status[o] = (uint8_t)code;
-        if (RAGGED && code != 0 && err != nullptr) atomicOr(err, code);
+#include "cos_finish.inc"
       }
     }
   }
@@ -413,39 +287,20 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------
 constexpr int kTopkThreads = 256;
 
-__device__ __forceinline__ uint32_t desc_key(float f) {
-  if (f != f) return 0xFFFFFFFFu;  // NaN: after everything
-  uint32_t u = __float_as_uint(f);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending-orderable
-  return ~u;                                       // descending, and never 0xFFFFFFFF for non-NaN? (-inf -> 0xFF800000 -> fine)
-}
-
 __global__ __launch_bounds__(kTopkThreads) void topk_kernel(const float* __restrict__ scores, int c, int cpad, int k,
                                                             int32_t* __restrict__ order, float* __restrict__ sorted) {
   extern __shared__ __attribute__((aligned(16))) uint64_t items[];
   const int qi = blockIdx.x;
   const float* s = scores + (int64_t)qi * c;
-  for (int t = threadIdx.x; t < cpad; t += kTopkThreads) {
-    uint64_t v = ~0ull;  // padding sorts after every real item (position field > any real position)
-    if (t < c) v = ((uint64_t)desc_key(s[t]) << 32) | (uint32_t)t;
-    items[t] = v;
-  }
+  for (int t = threadIdx.x; t < cpad; t += kTopkThreads)
+    items[t] = t < c ? desc_item(s[t], (uint32_t)t) : ~0ull;   // (padding: behind every real item)
   __syncthreads();
-  for (int size = 2; size <= cpad; size <<= 1) {
+  constexpr int kPassThreads = kTopkThreads, base = 0;
+  const int n = cpad;
+  for (int size = 2; size <= cpad; size <<= 1)
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < (cpad >> 1); t += kTopkThreads) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool up = ((lo & size) == 0);
-        const uint64_t a = items[lo], b = items[hi];
-        if ((a > b) == up) {
-          items[lo] = b;
-          items[hi] = a;
-        }
-      }
-      __syncthreads();
+#include "bitonic_pass.inc"
     }
-  }
   for (int t = threadIdx.x; t < k; t += kTopkThreads) {
     const uint32_t pos = (uint32_t)items[t];
     order[(int64_t)qi * k + t] = (int32_t)pos;
@@ -460,40 +315,29 @@ __global__ void topk_fill_kernel(const float* __restrict__ scores, int c, int64_
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= cpad) return;
   const int qi = blockIdx.y;
-  uint64_t v = ~0ull;
-  if (t < c) v = ((uint64_t)desc_key(scores[(int64_t)qi * c + t]) << 32) | (uint32_t)t;
-  items[(int64_t)qi * cpad + t] = v;
+  items[(int64_t)qi * cpad + t] = t < c ? desc_item(scores[(int64_t)qi * c + t], (uint32_t)t) : ~0ull;
 }
 
 // All compare-exchange steps with stride < kTopkChunk of one merge size (or, with full = true, the whole
 // network up to size kTopkChunk) on a chunk held in LDS.  Direction follows the GLOBAL index.
-__global__ __launch_bounds__(kTopkThreads) void topk_local_kernel(uint64_t* __restrict__ items, int64_t cpad, int64_t size,
+__global__ __launch_bounds__(kTopkThreads) void topk_local_kernel(uint64_t* __restrict__ rows, int64_t cpad, int64_t merge,
                                                                   bool full) {
-  __shared__ uint64_t buf[kTopkChunk];
+  __shared__ uint64_t items[kTopkChunk];
+  constexpr int kPassThreads = kTopkThreads, n = kTopkChunk;
   const int qi = blockIdx.y;
   const int64_t base = (int64_t)blockIdx.x * kTopkChunk;
-  uint64_t* g = items + (int64_t)qi * cpad + base;
-  for (int t = threadIdx.x; t < kTopkChunk; t += kTopkThreads) buf[t] = g[t];
+  uint64_t* g = rows + (int64_t)qi * cpad + base;
+  for (int t = threadIdx.x; t < kTopkChunk; t += kTopkThreads) items[t] = g[t];
   __syncthreads();
-  const int64_t first = full ? 2 : size;
-  const int64_t last = full ? kTopkChunk : size;
-  for (int64_t sz = first; sz <= last; sz <<= 1) {
-    const int top = (int)((sz < (int64_t)kTopkChunk ? sz : (int64_t)kTopkChunk) >> 1);
+  const int64_t first = full ? 2 : merge;
+  const int64_t last = full ? kTopkChunk : merge;
+  for (int64_t size = first; size <= last; size <<= 1) {
+    const int top = (int)((size < (int64_t)kTopkChunk ? size : (int64_t)kTopkChunk) >> 1);
     for (int stride = top; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < (kTopkChunk >> 1); t += kTopkThreads) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool up = (((base + lo) & sz) == 0);
-        const uint64_t a = buf[lo], b = buf[hi];
-        if ((a > b) == up) {
-          buf[lo] = b;
-          buf[hi] = a;
-        }
-      }
-      __syncthreads();
+#include "bitonic_pass.inc"
     }
   }
-  for (int t = threadIdx.x; t < kTopkChunk; t += kTopkThreads) g[t] = buf[t];
+  for (int t = threadIdx.x; t < kTopkChunk; t += kTopkThreads) g[t] = items[t];
 }
 
 __global__ void topk_global_step_kernel(uint64_t* __restrict__ items, int64_t cpad, int64_t size, int64_t stride) {
@@ -543,63 +387,60 @@ int lshrs_sort_u64_rows(uint64_t* items, int q, int64_t cpad, hipStream_t s) {
 }
 
 namespace {
-// The launchers behind the ten lshrs_cosine_{batch,ragged}_{f32,bf16,f16,i8,f8e4m3} entries: argument checks (before anything
-// touches a device), slicing and the choice of the aligned path, written once for every corpus element type.
+// The launcher behind the ten lshrs_cosine_{batch,ragged}_{f32,bf16,f16,i8,f8e4m3} entries, written once for every corpus element
+// type and both forms: argument checks (before anything touches a device), slicing, the choice of the aligned path, the launch.
+// Batch: c candidates for each query, listed at cand (or, cand == NULL, rows qi * c ..), a status byte each.  RAGGED: `total`
+// candidates in all, query qi's row_cnt[qi] at row_off[qi] of cand, what is wrong with them in err.
+//
+// Slices per query: enough workgroups to fill 256 CUs several times over even for a single query - doubled while the launch
+// has fewer than 4096 workgroups and a slice of a list of `len` more than two rounds of a workgroup's rows in flight, up to `cap`.
 template <typename E>
-int cosine_batch(const typename CosElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
-                 const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus, void* stream) {
-  if (q == 0 || c == 0) return 0;
-  if (corpus == nullptr || queries == nullptr || scores == nullptr || m <= 0 || dim <= 0 || q < 0 || c < 0 || ldc < dim)
+int cos_slices(int32_t q, int64_t len, int cap) {
+  const int per_block = kCosWaves * CosElem<E>::kInflight;
+  int slices = 1;
+  while ((int64_t)q * slices < 4096 && (len + slices - 1) / slices > 2 * per_block && slices < cap) slices *= 2;
+  return slices;
+}
+
+template <typename E, bool RAGGED>
+int cosine_launch(const typename CosElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                  const int64_t* cand, int32_t c, const int64_t* row_off, const int32_t* row_cnt, int64_t total, float* scores,
+                  uint8_t* status, uint8_t* qstatus, int32_t* err, void* stream) {
+  const int64_t n = RAGGED ? total : c;
+  if (q == 0 || n == 0) return 0;
+  if (corpus == nullptr || queries == nullptr || scores == nullptr || m <= 0 || dim <= 0 || q < 0 || n < 0 || ldc < dim ||
+      (RAGGED && (cand == nullptr || row_off == nullptr || row_cnt == nullptr)))
     return LSHRS_E_BADARG;
   if (dim > 16384) return LSHRS_E_TOOLARGE;
-  if (cand_idx == nullptr && (int64_t)q * c > m) return LSHRS_E_BADARG;
-  // enough workgroups to fill 256 CUs several times over even for a single query
-  int slices = 1;
-  const int per_block = kCosWaves * CosElem<E>::kInflight;
-  while ((int64_t)q * slices < 4096 && (c + slices - 1) / slices > 2 * per_block) slices *= 2;
+  if (!RAGGED && cand == nullptr && (int64_t)q * c > m) return LSHRS_E_BADARG;
+  // from the list every query has; RAGGED: from the AVERAGE list (the lists of one batch are alike: a bucket per band each),
+  // and no more than 1024
+  const int slices = RAGGED ? cos_slices<E>(q, (total + q - 1) / q, 1024) : cos_slices<E>(q, c, INT32_MAX);
   if ((int64_t)q * slices > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
   constexpr int kVec = CosElem<E>::kVec;
   const bool aligned = (dim % kVec == 0) && (ldc % kVec == 0) && ((reinterpret_cast<uintptr_t>(corpus) & 15) == 0);
   const size_t shmem = (size_t)(((dim + 3) & ~3) + kCosWaves) * sizeof(float);
   const dim3 grid((unsigned)((int64_t)q * slices)), block(kCosThreads);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (aligned)
-    hipLaunchKernelGGL((cosine_kernel<E, true, false>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_idx, c, slices,
-                       scores, status, qstatus, nullptr, nullptr, nullptr);
-  else
-    hipLaunchKernelGGL((cosine_kernel<E, false, false>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_idx, c, slices,
-                       scores, status, qstatus, nullptr, nullptr, nullptr);
+  dispatch_bool(aligned, [&](auto al) {
+    hipLaunchKernelGGL((cosine_kernel<E, decltype(al)::value, RAGGED>), grid, block, shmem, static_cast<hipStream_t>(stream),
+                       corpus, m, ldc, dim, queries, cand, RAGGED ? 0 : c, slices, scores, status, qstatus, row_off, row_cnt, err);
+  });
   return -(int)hipGetLastError();
+}
+
+template <typename E>
+int cosine_batch(const typename CosElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
+                 const int64_t* cand_idx, int32_t c, float* scores, uint8_t* status, uint8_t* qstatus, void* stream) {
+  return cosine_launch<E, false>(corpus, m, ldc, dim, queries, q, cand_idx, c, nullptr, nullptr, 0, scores, status, qstatus, nullptr,
+                                 stream);
 }
 
 template <typename E>
 int cosine_ragged(const typename CosElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const float* queries, int32_t q,
                   const int64_t* cand_rows, const int64_t* row_off, const int32_t* row_cnt, int64_t total, float* scores,
                   int32_t* err, void* stream) {
-  if (q == 0 || total == 0) return 0;
-  if (corpus == nullptr || queries == nullptr || cand_rows == nullptr || row_off == nullptr || row_cnt == nullptr ||
-      scores == nullptr || m <= 0 || dim <= 0 || q < 0 || total < 0 || ldc < dim)
-    return LSHRS_E_BADARG;
-  if (dim > 16384) return LSHRS_E_TOOLARGE;
-  // slices per query from the AVERAGE list (the lists of one batch are alike: a bucket per band each): enough workgroups to
-  // fill 256 CUs several times over even for a handful of queries
-  int slices = 1;
-  const int per_block = kCosWaves * CosElem<E>::kInflight;
-  const int64_t avg = (total + q - 1) / q;
-  while ((int64_t)q * slices < 4096 && (avg + slices - 1) / slices > 2 * per_block && slices < 1024) slices *= 2;
-  if ((int64_t)q * slices > 0x7fffffffLL) return LSHRS_E_TOOLARGE;
-  constexpr int kVec = CosElem<E>::kVec;
-  const bool aligned = (dim % kVec == 0) && (ldc % kVec == 0) && ((reinterpret_cast<uintptr_t>(corpus) & 15) == 0);
-  const size_t shmem = (size_t)(((dim + 3) & ~3) + kCosWaves) * sizeof(float);
-  const dim3 grid((unsigned)((int64_t)q * slices)), block(kCosThreads);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (aligned)
-    hipLaunchKernelGGL((cosine_kernel<E, true, true>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_rows, 0, slices,
-                       scores, nullptr, nullptr, row_off, row_cnt, err);
-  else
-    hipLaunchKernelGGL((cosine_kernel<E, false, true>), grid, block, shmem, s, corpus, m, ldc, dim, queries, cand_rows, 0, slices,
-                       scores, nullptr, nullptr, row_off, row_cnt, err);
-  return -(int)hipGetLastError();
+  return cosine_launch<E, true>(corpus, m, ldc, dim, queries, q, cand_rows, 0, row_off, row_cnt, total, scores, nullptr, nullptr, err,
+                                stream);
 }
 
 template <typename E>
@@ -725,15 +566,9 @@ int lshrs_topk_desc_f32(const float* scores, int32_t q, int32_t c, int32_t k, in
   if (q > 65535) return LSHRS_E_TOOLARGE;
   uint64_t* items = static_cast<uint64_t*>(workspace);
   const int64_t cpad = topk_pad(c);
-  const dim3 qgrid((unsigned)((cpad + 255) / 256), (unsigned)q), half((unsigned)(((cpad >> 1) + 255) / 256), (unsigned)q);
-  const dim3 chunks((unsigned)(cpad / kTopkChunk), (unsigned)q);
-  hipLaunchKernelGGL(topk_fill_kernel, qgrid, dim3(256), 0, s, scores, c, cpad, items);
-  hipLaunchKernelGGL(topk_local_kernel, chunks, dim3(kTopkThreads), 0, s, items, cpad, (int64_t)kTopkChunk, true);
-  for (int64_t size = 2 * (int64_t)kTopkChunk; size <= cpad; size <<= 1) {
-    for (int64_t stride = size >> 1; stride >= kTopkChunk; stride >>= 1)
-      hipLaunchKernelGGL(topk_global_step_kernel, half, dim3(256), 0, s, items, cpad, size, stride);
-    hipLaunchKernelGGL(topk_local_kernel, chunks, dim3(kTopkThreads), 0, s, items, cpad, size, false);
-  }
+  hipLaunchKernelGGL(topk_fill_kernel, dim3((unsigned)((cpad + 255) / 256), (unsigned)q), dim3(256), 0, s, scores, c, cpad, items);
+  const int rc = lshrs_sort_u64_rows(items, q, cpad, s);
+  if (rc) return rc;
   hipLaunchKernelGGL(topk_emit_kernel, dim3((unsigned)((k + 255) / 256), (unsigned)q), dim3(256), 0, s, scores, items, c,
                      cpad, k, order, sorted);
   return -(int)hipGetLastError();

@@ -29,8 +29,10 @@
 // (scan_pass.inc) - and the head of a finished tile (scan_tile_head).  The two emitting kernels: scoring and marking a tile
 // (scan_mark) and writing its hits through the cursor (scan_emit); on the host their common refusals and the cursor's reset
 // (scan_emit_begin).  The three plans: scan_rows_geometry and scan_front_bytes.
+// The element types of a row, their exact conversions to f32 (a lone element, a dword's elements), the wave's sum and the
+// orderable key of a score are not this unit's own: lshrs_rows.h, shared with the rerank (rerank.hip).
 // ABI and reference citations: include/lshrs_hip.h.  Design notes, the epsilon derivation and the roof: DESIGN.md.
-#include "lshrs_common.h"
+#include "lshrs_rows.h"
 
 #include <type_traits>
 
@@ -47,36 +49,18 @@ constexpr int kScanChunkBytes = kScanQTile * kScanKChunk * 2 * 2;   // both term
 constexpr int kScanMaxDim = 16384;
 constexpr int kScanMergeItems = 8192; // slices * window a merge workgroup sorts in LDS (64 KiB)
 
-struct Bf16 {};
-struct F16 {};
-struct I8 {};
-struct F8E4M3 {};
-
-// per element type: what a row holds, bf16 terms per element, 16-B vectors behind a lane's 32 elements of a chunk
-template <typename E> struct ScanElem;
-template <> struct ScanElem<float> { using T = float; static constexpr int kTerms = 2, kVecs = 8, kAlign = 4; };
-template <> struct ScanElem<Bf16> { using T = uint16_t; static constexpr int kTerms = 1, kVecs = 4, kAlign = 8; };
-template <> struct ScanElem<F16> { using T = uint16_t; static constexpr int kTerms = 2, kVecs = 4, kAlign = 8; };
-template <> struct ScanElem<I8> { using T = int8_t; static constexpr int kTerms = 1, kVecs = 2, kAlign = 16; };
-template <> struct ScanElem<F8E4M3> { using T = uint8_t; static constexpr int kTerms = 1, kVecs = 2, kAlign = 16; };
+// per element type (lshrs_rows.h: the tags, RowT<E>, the conversions): bf16 terms per element (bf16, int8 and e4m3fn are exact
+// in bf16; f16 and f32 enter as two), and what a lane's 32 elements of a chunk are in 16-B vectors and need in alignment
+template <typename E> struct ScanElem {
+  using T = RowT<E>;
+  static constexpr int kTerms = (std::is_same_v<E, float> || std::is_same_v<E, F16>) ? 2 : 1;
+  static constexpr int kVecs = 8 / kRowPerDword<E>, kAlign = 4 * kRowPerDword<E>;
+};
 
 template <typename E> struct ScanRaw { u32x4 v[ScanElem<E>::kVecs]; };   // 32 elements as they lie in memory
 
-__device__ __forceinline__ float scan_wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// ascending-orderable bits of a score; an item = {key, ~row}: larger = better score, then lower row.  0 = no item (every real
-// key is above 0: the key of -inf is 0x007fffff).
-__device__ __forceinline__ uint32_t scan_key(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float scan_unkey(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+// an item of the selection = {asc_key(score), ~row}: larger = better score, then lower row.  0 = no item (every real key is
+// above 0).
 
 // ------------------------------------------------------------------------------------------
 // queries -> B fragments and norms, one text for both kinds of query: rows of f32 (the `float` instantiation: src = the
@@ -84,12 +68,6 @@ __device__ __forceinline__ float scan_unkey(uint32_t k) {
 // self-join: src = the corpus, its ld and row_ids).  An element is converted to f32 exactly, then split and summed in one
 // order whatever it was, so an approximate score of the self-join is the one the same rows get as f32 queries.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float scan_elem_f32(float, float v) { return v; }
-__device__ __forceinline__ float scan_elem_f32(Bf16, uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ float scan_elem_f32(F16, uint16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
-__device__ __forceinline__ float scan_elem_f32(I8, int8_t v) { return (float)v; }
-__device__ __forceinline__ float scan_elem_f32(F8E4M3, uint8_t v) { return __builtin_amdgcn_cvt_f32_fp8((int)v, 0); }
-
 // Workspace image: [qtile][chunk][term < kTerms][step s][column block cb][lane] x 16 bytes; lane (c = l & 31, h = l >> 5)
 // holds query qtile * 64 + cb * 32 + c at k = chunk * 64 + 32 h + 8 s + j, j = 0 .. 7.  Zero beyond qn and dim, and for a
 // dead row.  A one-term element is exact in bf16: its mid term is zero and the image holds hi only (half the bytes).
@@ -110,7 +88,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_image_kernel(const typename
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int k = kbase + j;
-      const float v = (ok && k < dim) ? scan_elem_f32(E{}, row[k]) : 0.f;
+      const float v = (ok && k < dim) ? row_elem_f32(E{}, row[k]) : 0.f;
       const uint32_t b = __float_as_uint(v) & 0xffff0000u;
       hb[j] = b >> 16;
       mb[j] = __float_as_uint(v - __uint_as_float(b)) >> 16;
@@ -140,11 +118,11 @@ __global__ __launch_bounds__(kScanThreads) void scan_norm_kernel(const typename 
   if (ok) {
     const typename ScanElem<E>::T* row = src + (qb + qi) * ld;
     for (int k = lane; k < dim; k += 64) {
-      const float v = scan_elem_f32(E{}, row[k]);
+      const float v = row_elem_f32(E{}, row[k]);
       ss = __builtin_fmaf(v, v, ss);
     }
   }
-  ss = scan_wave_sum(ss);
+  ss = wave_sum(ss);
   if (lane == 0) {
     const float n = ok ? sqrtf(ss) : 1.f;
     qnorm[qi] = n;
@@ -168,7 +146,7 @@ __device__ __forceinline__ ScanRaw<E> scan_load_vec(const typename ScanElem<E>::
 template <typename E>
 __device__ __forceinline__ ScanRaw<E> scan_load_elems(const typename ScanElem<E>::T* row, int k0, int dim) {
   using T = typename ScanElem<E>::T;
-  constexpr int kPer = 4 / (int)sizeof(T);            // elements per dword
+  constexpr int kPer = kRowPerDword<E>;
   ScanRaw<E> r;
 #pragma unroll
   for (int i = 0; i < ScanElem<E>::kVecs; ++i)
@@ -190,57 +168,40 @@ __device__ __forceinline__ ScanRaw<E> scan_load_elems(const typename ScanElem<E>
   return r;
 }
 
-// the eight elements of MFMA step s as f32 (exact)
-__device__ __forceinline__ void scan_elems8(float, const ScanRaw<float>& r, int s, float (&x)[8]) {
+// the eight elements of MFMA step s as f32 (exact): the 8 / kPer dwords behind them, each unpacked in memory order
+template <typename E>
+__device__ __forceinline__ void scan_elems8(const ScanRaw<E>& r, int s, float (&x)[8]) {
+  constexpr int kPer = kRowPerDword<E>, kDwords = 8 / kPer;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) x[j] = __uint_as_float(r.v[2 * s + (j >> 2)][j & 3]);
-}
-__device__ __forceinline__ void scan_elems8(F16, const ScanRaw<F16>& r, int s, float (&x)[8]) {
+  for (int d = 0; d < kDwords; ++d) {
+    const int w = s * kDwords + d;                    // the dword among the 32 elements'
+    float e[kPer];
+    row_unpack(E{}, r.v[w >> 2][w & 3], e);
 #pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    const uint32_t w = r.v[s][d];
-    x[2 * d] = (float)__builtin_bit_cast(_Float16, (uint16_t)w);
-    x[2 * d + 1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
-  }
-}
-__device__ __forceinline__ void scan_elems8(I8, const ScanRaw<I8>& r, int s, float (&x)[8]) {
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    const uint32_t w = r.v[s >> 1][(s & 1) * 2 + d];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[4 * d + j] = (float)(int8_t)(w >> (8 * j));
-  }
-}
-__device__ __forceinline__ void scan_elems8(F8E4M3, const ScanRaw<F8E4M3>& r, int s, float (&x)[8]) {
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    const uint32_t w = r.v[s >> 1][(s & 1) * 2 + d];
-    x[4 * d + 0] = __builtin_amdgcn_cvt_f32_fp8((int)w, 0);
-    x[4 * d + 1] = __builtin_amdgcn_cvt_f32_fp8((int)w, 1);
-    x[4 * d + 2] = __builtin_amdgcn_cvt_f32_fp8((int)w, 2);
-    x[4 * d + 3] = __builtin_amdgcn_cvt_f32_fp8((int)w, 3);
+    for (int j = 0; j < kPer; ++j) x[kPer * d + j] = e[j];
   }
 }
 
 // raw elements -> the A fragments of the four steps (hi; mid for the two-term types) and += ||x||^2
 template <typename E>
 __device__ __forceinline__ void scan_fragments(const ScanRaw<E>& r, u32x4 (&hi)[4], u32x4 (&mid)[4], float& nn) {
-  if constexpr (std::is_same_v<E, Bf16>) {
+  if constexpr (std::is_same_v<E, Bf16>) {          // (the stored bits ARE the fragment)
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       hi[s] = r.v[s];
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
-        const float a = __uint_as_float(r.v[s][d] << 16), b = __uint_as_float(r.v[s][d] & 0xffff0000u);
-        nn = __builtin_fmaf(a, a, nn);
-        nn = __builtin_fmaf(b, b, nn);
+        float e[2];
+        row_unpack(Bf16{}, r.v[s][d], e);
+        nn = __builtin_fmaf(e[0], e[0], nn);
+        nn = __builtin_fmaf(e[1], e[1], nn);
       }
     }
   } else {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       float x[8];
-      scan_elems8(E{}, r, s, x);
+      scan_elems8<E>(r, s, x);
       uint32_t hb[8], mb[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -380,7 +341,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
           const float rn = __shfl(xn, rr);
           const float sc = acc[t][cb][i] / (rn * qn[cb]);
           acc[t][cb][i] = sc;
-          const uint64_t it = ((uint64_t)scan_key(sc) << 32) | (rowlo - (uint32_t)((i & 3) + 8 * (i >> 2)));
+          const uint64_t it = key_item(asc_key(sc), rowlo - (uint32_t)((i & 3) + 8 * (i >> 2)));
           if (qok[cb] && ((livemask >> rr) & 1u) && sc == sc && it > bar) pend |= 1u << i;
         }
         for (;;) {
@@ -389,7 +350,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
             if (pend & (1u << i)) {
               const int pos = atomicAdd(&cnt[qc], 1);
               if (pos < cap) {
-                buf[pos] = ((uint64_t)scan_key(acc[t][cb][i]) << 32) | (rowlo - (uint32_t)((i & 3) + 8 * (i >> 2)));
+                buf[pos] = key_item(asc_key(acc[t][cb][i]), rowlo - (uint32_t)((i & 3) + 8 * (i >> 2)));
                 pend &= ~(1u << i);
               }
             }
@@ -401,7 +362,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
           bar = thr[qc];
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            const uint64_t it = ((uint64_t)scan_key(acc[t][cb][i]) << 32) | (rowlo - (uint32_t)((i & 3) + 8 * (i >> 2)));
+            const uint64_t it = key_item(asc_key(acc[t][cb][i]), rowlo - (uint32_t)((i & 3) + 8 * (i >> 2)));
             if (!(it > bar)) pend &= ~(1u << i);
           }
         }
@@ -659,7 +620,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_merge_kernel(const uint64_t
     const uint64_t v = merge_items[t];
     have += v != 0ull ? 1 : 0;
     out_rows[(int64_t)qi * window + t] = v != 0ull ? (int64_t)(0xffffffffu - (uint32_t)v) : -1;
-    out_approx[(int64_t)qi * window + t] = v != 0ull ? scan_unkey((uint32_t)(v >> 32)) : -__builtin_inff();
+    out_approx[(int64_t)qi * window + t] = v != 0ull ? asc_unkey((uint32_t)(v >> 32)) : -__builtin_inff();
   }
   if (have) atomicAdd(&total, have);
   __syncthreads();
