@@ -23,6 +23,10 @@ rerank_rounding)``, which no row of the answer can lie below, and the rerank's k
 a threshold - the stored rows are their own queries, every unordered pair is multiplied once, and the rerank's kernel judges what
 the pass lets through, the row of the lower id as the query.
 
+``exact_knn`` is the k-NN self-join on the top-k pass (``lshrs_scan_knn_*``): for every live row the ``k`` OTHER live rows
+nearest to it - the stored rows are their own queries, a block at a time, no row enters its own window, and the settle rule and
+the gather fallback are those of ``exact_top_k``.
+
 No CPU compute path: the host moves arrays, decides which queries are settled from three numbers per query, and keeps counts.
 """
 
@@ -36,7 +40,7 @@ from . import _native
 from .similarity import (_CORPUS_ENTRY, _CORPUS_ENTRY_8BIT, _on_device, _raise_for_status, corpus_suffix, cosine_ragged_device,
                          cosine_scores_device, topk_desc_device)
 
-__all__ = ["exact_top_k", "exact_above", "exact_pairs_above", "settled", "choose_window", "rerank_rounding", "scan_epsilon",
+__all__ = ["exact_top_k", "exact_above", "exact_pairs_above", "exact_knn", "scan_knn", "settled", "choose_window", "rerank_rounding", "scan_epsilon",
            "scan_max_window", "scan_windows", "scan_above", "scan_pairs", "above_bars", "above_recall"]
 
 METHODS = ("auto", "scan", "gather")
@@ -588,6 +592,151 @@ def exact_pairs_above(corpus, threshold, *, row_ids=None, max_pairs: int = 1 << 
                 ids_a, ids_b, scores = ia[order].contiguous(), ib[order].contiguous(), exact[order].contiguous()
                 out["kept"] = int(ids_a.shape[0])
     return _finish(stats, out, (ids_a, ids_b, scores), return_tensors)
+
+
+# ------------------------------------------------------------------------------------------
+# k-NN self-join: the k nearest OTHER live rows of every live row
+# ------------------------------------------------------------------------------------------
+def scan_knn(corpus, q_begin: int, q_count: int, window: int, row_ids=None, qblock: int = 0):
+    """Device-level entry of the k-NN self-join's first pass (``lshrs_scan_knn_*``): ``corpus`` / ``row_ids`` as
+    :func:`scan_windows` takes them, the rows ``[q_begin, q_begin + q_count)`` of the corpus as the queries, ``qblock`` the rows
+    taken as queries per launch (0: the library's plan; else a multiple of 64).  Returns ``(rows (q_count, window) int64, approx
+    (q_count, window) float32, count (q_count,) int32, err int32[1])`` as :func:`scan_windows` does: per query row the
+    ``window`` other live rows of the largest approximate score; count 0 for a dead query row."""
+    torch = _native.require_gpu()
+    lib = _native.load()
+    entry = "lshrs_scan_knn_" + corpus_suffix(corpus)
+    dev = corpus.device
+    q_begin, q, window, qblock = int(q_begin), int(q_count), int(window), int(qblock)
+    m, dim = int(corpus.shape[0]), int(corpus.shape[1])
+    rows = torch.empty((max(q, 0), window), dtype=torch.int64, device=dev)
+    approx = torch.empty((max(q, 0), window), dtype=torch.float32, device=dev)
+    count = torch.empty((max(q, 0),), dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws = _scan_workspace(torch, lib, "lshrs_scan_knn_workspace_bytes", dev, q, m, dim, window, qblock)
+        _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim,
+                                          row_ids.data_ptr() if row_ids is not None else None, q_begin, q, window, qblock,
+                                          rows.data_ptr(), approx.data_ptr(), count.data_ptr(), ws.data_ptr(), err.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream), entry)
+    return rows, approx, count, err
+
+
+def _knn_chunk(block: int, dim: int, window: int) -> int:
+    """Query rows of one chunk of ``exact_knn``'s scan: whole blocks (at least one) whose float32 copy and windows - rows and
+    two score arrays - stay under ``_PAIRS_QUERY_BYTES``."""
+    return max(1, _PAIRS_QUERY_BYTES // (4 * int(dim) + 16 * int(window)) // int(block)) * int(block)
+
+
+def _drop_self(torch, g_ids, own):
+    """``g_ids`` (u, kk + 1) without each row's own id ``own`` (u,), or without its last entry where the own id is not in it -
+    more than ``kk`` exact duplicates of lower id pushed it out: the mask ``(u, kk + 1)`` of what stays, ``kk`` a row."""
+    is_self = g_ids == own.unsqueeze(1)
+    last = int(g_ids.shape[1]) - 1
+    drop = torch.where(is_self.any(dim=1), is_self.to(torch.int32).argmax(dim=1), torch.full_like(own, last))
+    return torch.arange(last + 1, device=g_ids.device).unsqueeze(0) != drop.unsqueeze(1)
+
+
+def exact_knn(corpus, k: int, *, row_ids=None, method: str = "auto", return_tensors: bool = False,
+              stats: Optional[Dict] = None):
+    """The ``k`` OTHER rows of ``corpus`` nearest to every row by cosine, exactly - the k-NN graph of the stored vectors:
+    ``(ids (n,) int64, neighbors (n, kk) int64, scores (n, kk) float32)``; ``n``: the live rows, in ascending order of their
+    ids; ``kk = min(k, n - 1)`` (0 when ``n <= 1``); per row scores descending, equal scores by ascending id; a row is never its
+    own neighbour.  NumPy arrays, or device tensors with ``return_tensors``.
+
+    ``corpus``, ``row_ids``: as :func:`exact_top_k` takes them (live entries of ``row_ids`` are taken to be distinct).
+    ``scores[i, j]`` is the RERANK score with row ``ids[i]``, converted to float32, as the query and row ``neighbors[i, j]`` as
+    the row - bit for bit what ``exact_top_k(corpus.float(), corpus, ...)`` returns for that pair.  The score is oriented, not
+    symmetrised (see :func:`exact_pairs_above`): ``scores`` of (a, b) and of (b, a) may differ in the last bit.
+
+    ``method``: "scan" - the query rows go in chunks of whole blocks whose windows and float32 copy stay bounded; per chunk one
+    pass over all rows on the matrix cores (``lshrs_scan_knn_*``: the rows themselves are the queries, no float32 copy is made
+    for the pass and one-term rows issue one MFMA per step) keeps a window of other rows per row, the window is rescored by the
+    rerank's kernel and a row is settled as :func:`settled` says - ``count < window`` here meaning that every OTHER live row
+    was seen; the rows it does not settle go through "gather".  "gather" - every row, as a float32 query, scores every live
+    row with the rerank's kernels for ``kk + 1`` and the row itself is removed - or the last entry, where more than ``kk``
+    duplicates of lower id pushed it out.  "auto" - "scan" while ``2 k`` fits the widest window, else "gather".
+    ``stats``: a dict that receives ``rows``, ``live``, ``settled_first_pass``, ``gathered``, ``window``, ``epsilon`` and
+    ``chunks``.
+
+    ``k <= 0`` or a bad ``method`` raises ``ValueError`` before anything touches the GPU; a live row of zero norm raises
+    ``ValueError("Cannot normalize zero vector")``; rows beyond the kernels raise the ``NativeLibraryError``
+    :func:`exact_top_k` raises."""
+    _check_method(method)
+    if int(k) <= 0:
+        raise ValueError("k must be > 0")
+    k = int(k)
+    torch = _native.require_gpu()
+    lib = _native.load()
+    corpus_suffix(corpus)
+    dev = corpus.device
+    with torch.cuda.device(dev):
+        d_ids = _rows_args(torch, corpus, row_ids, "exact_knn")
+        m, dim = int(corpus.shape[0]), int(corpus.shape[1])
+        # the live rows in ascending order of their ids: the order of the answer, and the gather's tie rule
+        if d_ids is None:
+            live_rows = torch.arange(m, dtype=torch.int64, device=dev)
+            live_ids = live_rows
+        else:
+            live_rows = torch.nonzero(d_ids >= 0).reshape(-1)
+            live_ids = d_ids[live_rows]
+            by_id = torch.argsort(live_ids)
+            live_rows, live_ids = live_rows[by_id].contiguous(), live_ids[by_id].contiguous()
+        n = int(live_rows.shape[0])
+        kk = max(0, min(k, n - 1))
+        max_window = scan_max_window()
+        use_scan = method == "scan" or (method == "auto" and 2 * k <= max_window)
+        window = choose_window(k, max_window)
+        eps = scan_epsilon(corpus.dtype, dim)
+        out = {"rows": m, "live": n, "settled_first_pass": 0, "gathered": 0, "window": window if use_scan else 0,
+               "epsilon": eps, "chunks": 0}
+        neighbors = torch.empty((n, kk), dtype=torch.int64, device=dev)
+        scores = torch.empty((n, kk), dtype=torch.float32, device=dev)
+        if kk:
+            block = _pairs_block(lib, m, dim)
+            chunk = _knn_chunk(block, dim, window) if use_scan else max(1, _PAIRS_QUERY_BYTES // (4 * dim))
+            # where the answer of the row at each position goes (-1: a dead row)
+            slot = torch.full((m,), -1, dtype=torch.int64, device=dev)
+            slot[live_rows] = torch.arange(n, dtype=torch.int64, device=dev)
+            for lo in range(0, m, chunk):
+                hi = min(m, lo + chunk)
+                out["chunks"] += 1
+                mine = torch.nonzero(slot[lo:hi] >= 0).reshape(-1)             # the chunk's live rows, by position
+                if not int(mine.numel()):
+                    continue
+                pos = mine + lo
+                queries = _rows_as_f32(torch, corpus, pos)
+                todo = None                                 # rows of `mine` left to the gather: None = all of them
+                if use_scan:
+                    rows, approx, count, err = scan_knn(corpus, lo, hi - lo, window, d_ids)
+                    rows, approx, count = rows[mine], approx[mine], count[mine].contiguous()
+                    # the window in ascending order of id (padding last): the tie rule of the top-k kernel then is ascending id
+                    wid = rows if d_ids is None else torch.where(rows >= 0, d_ids[rows.clamp(min=0)], rows)
+                    key = torch.where(rows >= 0, wid, torch.full_like(wid, torch.iinfo(torch.int64).max))
+                    by_id = torch.argsort(key, dim=1)
+                    rows_s, wid = torch.gather(rows, 1, by_id).contiguous(), torch.gather(wid, 1, by_id)
+                    exact, err2 = _rescore(torch, corpus, queries, rows_s, count)
+                    if int(err.item()) & 5 or int(err2.item()) & 5:
+                        raise ValueError("Cannot normalize zero vector")
+                    kw = min(kk, window)
+                    order, best = topk_desc_device(exact, kw)
+                    s_k = best[:, kw - 1] if kw == kk else torch.full((int(mine.numel()),), float("-inf"), device=dev)
+                    done = settled(count.cpu().numpy(), window, approx[:, window - 1].cpu().numpy(), s_k.cpu().numpy(),
+                                   eps + rerank_rounding(dim))
+                    at = slot[pos]
+                    neighbors[at, :kw] = torch.gather(wid, 1, order.long())
+                    scores[at, :kw] = best
+                    out["settled_first_pass"] += int(done.sum())
+                    todo = torch.from_numpy(np.flatnonzero(~done)).to(dev)
+                if todo is None or int(todo.numel()):
+                    sub = queries if todo is None else queries[todo].contiguous()
+                    at = slot[pos] if todo is None else slot[pos[todo]]
+                    g_ids, g_scores = _gather(torch, corpus, sub, live_rows, live_ids, kk + 1)
+                    stay = _drop_self(torch, g_ids, live_ids[at])
+                    neighbors[at] = g_ids[stay].view(-1, kk)
+                    scores[at] = g_scores[stay].view(-1, kk)
+                    out["gathered"] += int(sub.shape[0])
+    return _finish(stats, out, (live_ids, neighbors, scores), return_tensors)
 
 
 def above_recall(truth_ids, truth_scores, truth_bounds, cand_ids, cand_bounds, num_bands: int, rows_per_band: int) -> Dict:

@@ -1,4 +1,4 @@
-"""ctypes binding of ``csrc/liblshrs_hip.so`` (the C ABI declared in ``include/lshrs_hip.h``).
+"""ctypes binding of ``csrc/liblshrs_hip.so`` (the C ABI declared in ``include/lshrs_hip.h`` and ``include/lshrs_knn.h``).
 
 There is no CPU implementation behind this module: if the shared library has not
 been built, or the ABI version does not match, loading raises — loudly — and so
@@ -248,6 +248,13 @@ def _declare(lib: ctypes.CDLL) -> None:
     for dt in SCAN_ELEMS:
         pairs = getattr(lib, "lshrs_scan_pairs_" + dt)
         pairs.argtypes, pairs.restype = [vp, i64, i64, i32, vp, f32, i32, i64, vp, vp, vp, vp, vp, vp, vp], c.c_int
+    # the k-NN self-join (include/lshrs_knn.h): (q_count, m, dim, window, qblock)
+    lib.lshrs_scan_knn_workspace_bytes.argtypes = [i32, i64, i32, i32, i32]
+    lib.lshrs_scan_knn_workspace_bytes.restype = i64
+    # (corpus, m, ldc, dim, row_ids, q_begin, q_count, window, qblock, out_rows, out_approx, out_count, workspace, err, stream)
+    for dt in SCAN_ELEMS:
+        knn = getattr(lib, "lshrs_scan_knn_" + dt)
+        knn.argtypes, knn.restype = [vp, i64, i64, i32, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp], c.c_int
     lib.lshrs_pipe_create.argtypes = [i32, i32, i32, i32, i32]
     lib.lshrs_pipe_create.restype = vp
     lib.lshrs_pipe_destroy.argtypes = [vp]
@@ -332,6 +339,15 @@ EXPORTS = (
     "lshrs_pipe_destroy",
     "lshrs_pipe_hash_f32",
 )
+# ... and what include/lshrs_knn.h declares beside them (additive to ABI 7)
+EXPORTS_KNN = (
+    "lshrs_scan_knn_workspace_bytes",
+    "lshrs_scan_knn_f32",
+    "lshrs_scan_knn_bf16",
+    "lshrs_scan_knn_f16",
+    "lshrs_scan_knn_i8",
+    "lshrs_scan_knn_f8e4m3",
+)
 
 
 def load() -> ctypes.CDLL:
@@ -356,7 +372,7 @@ def load() -> ctypes.CDLL:
             lib = ctypes.CDLL(LIBRARY)
         except OSError as exc:  # pragma: no cover - environment specific
             raise NativeLibraryError(f"cannot load {LIBRARY}: {exc}") from exc
-        for name in EXPORTS:
+        for name in EXPORTS + EXPORTS_KNN:
             if not hasattr(lib, name):
                 raise NativeLibraryError(f"{LIBRARY} does not export {name}; rebuild it")
         _declare(lib)

@@ -703,6 +703,21 @@ class LSHRS:
         with _gc_paused():
             return list(zip(ids_a.tolist(), ids_b.tolist(), scores.astype(np.float64).tolist()))
 
+    def neighbors_exact(self, top_k: int = 10, *, return_arrays: bool = False):
+        """The ``top_k`` OTHER indexed vectors nearest to every indexed vector by cosine, EXACTLY - the k-NN graph of what is
+        indexed: the self-join beside :meth:`search_exact`, over the same corpus (``lshrs_amd.exact_knn``) and with the same
+        errors where there is none.  Returns ``[(id, [(neighbour, score), ...]), ...]`` in ascending order of id, scores
+        descending and equal scores by ascending id - or ``(ids (n,), neighbors (n, kk), scores (n, kk))`` arrays with
+        ``return_arrays``.  ``last_search_stats`` tells what the call did."""
+        from ._exact import exact_knn
+
+        ids, nbrs, scores = self._search_corpus("neighbors_exact", lambda store, _, k: store.neighbors(k),
+                                                lambda _, table, k, stats: exact_knn(table, k, stats=stats), None, top_k)
+        if return_arrays:
+            return ids, nbrs, scores
+        with _gc_paused():
+            return [(i, list(zip(nb, sc))) for i, nb, sc in zip(ids.tolist(), nbrs.tolist(), scores.astype(np.float64).tolist())]
+
     def recall_above(self, vectors, threshold) -> Dict[str, Any]:
         """What the index finds of the pairs it is configured for, measured: the truth is :meth:`search_exact_above`
         ``(vectors, threshold)``, the candidates are :meth:`query_many` ``(vectors, top_k=None)`` - every id that shares a

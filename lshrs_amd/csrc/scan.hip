@@ -24,16 +24,23 @@
 // image and norms built straight from the rows, every unordered pair of live rows multiplied once (a block scans the rows from
 // its own first row on, a workgroup from its tile's; diagonal tiles masked lane by lane), one MFMA per step for the one-term
 // types, whose image holds no mid term (lshrs_amd.exact_pairs_above).
-// Every layer is written once.  All three kernels: the image and the norms of the queries, whatever they are made of
+// k-NN self-join (scan_kernel<E, ALIGNED, SELF = true>, lshrs_scan_knn_*): the top-k scan with a block of the stored rows
+// themselves as the queries - image and norms from the rows as in the self-join, one MFMA per step for the one-term types, a
+// row never pushed into its own window.  The FULL square, no triangle: a product would have to feed the window of its row side
+// too, and those windows (256 rows a pass, per workgroup) do not fit in LDS beside the 64 of the query tile.
+// Every layer is written once.  All four kernels: the image and the norms of the queries, whatever they are made of
 // (scan_image_kernel<Q>, scan_norm_kernel<Q>, launched by scan_front), the pass - rows in, dot products and norms out
-// (scan_pass.inc) - and the head of a finished tile (scan_tile_head).  The two emitting kernels: scoring and marking a tile
-// (scan_mark) and writing its hits through the cursor (scan_emit); on the host their common refusals and the cursor's reset
-// (scan_emit_begin).  The three plans: scan_rows_geometry and scan_front_bytes.
+// (scan_pass.inc) - and the head of a finished tile (scan_tile_head).  The selection, the slices' winners and the merge: one
+// text for f32 queries and for the rows as queries (scan_kernel, scan_merge_kernel; scan_select on the host).  The two
+// emitting kernels: scoring and marking a tile (scan_mark) and writing its hits through the cursor (scan_emit); on the host
+// their common refusals and the cursor's reset (scan_emit_begin).  The four plans: scan_rows_geometry and scan_front_bytes.
 // The element types of a row, their exact conversions to f32 (a lone element, a dword's elements), the wave's sum and the
 // orderable key of a score are not this unit's own: lshrs_rows.h, shared with the rerank (rerank.hip).
-// ABI and reference citations: include/lshrs_hip.h.  Design notes, the epsilon derivation and the roof: DESIGN.md.
+// ABI and reference citations: include/lshrs_hip.h, include/lshrs_knn.h.  Design notes, the epsilon derivation and the roof: DESIGN.md.
 #include "lshrs_rows.h"
+#include "lshrs_knn.h"
 
+#include <initializer_list>
 #include <type_traits>
 
 using namespace lshrs;
@@ -277,16 +284,26 @@ __device__ __forceinline__ float scan_tile_head(float nn, bool live, int h, int3
 
 // ------------------------------------------------------------------------------------------
 // the scan.  grid (slices, query tiles); dynamic LDS: B chunk | items [64][cap] | threshold [64] | count [64]
+// SELF (the k-NN self-join): the queries are the block [qb, qb + q) of the stored rows; the image holds the rows' own terms
+// (kBTerms = 1 for the one-term types: no mid MFMA, scan_pass.inc), a dead row of the block is nobody's query, and no row
+// enters its own window (by position).  Every block scans all of [0, m).
 // ------------------------------------------------------------------------------------------
-template <typename E, bool ALIGNED>
-__global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename ScanElem<E>::T* __restrict__ corpus, int64_t m,
+// SELF, workgroups per CU.  At two the SELF instantiations fill 256 VGPRs and spill 12 to 36 bytes a lane to scratch, as seven of
+// the ten others do; at one - the precedent of kScanPairsPerCu - the accumulators live in AGPRs and nothing is spilled.  Two was
+// chosen on the measurement (200 000 x 768, k = 10, the first pass): 202 against 290 ms for bf16 rows, 363 against 507 ms for
+// f32.  A selecting workgroup waits at more barriers than an emitting one (the ticket loop, the prunes), and at one per CU the
+// CU has nothing to do meanwhile (k-NN self-join).
+constexpr int kScanKnnPerCu = 2;
+
+template <typename E, bool ALIGNED, bool SELF = false>
+__global__ __launch_bounds__(kScanThreads, SELF ? kScanKnnPerCu : 2) void scan_kernel(const typename ScanElem<E>::T* __restrict__ corpus, int64_t m,
                                                             int64_t ldc, int dim, const int64_t* __restrict__ row_ids,
                                                             const u32x4* __restrict__ image, const float* __restrict__ qnorm,
                                                             int q, int window, int cap, int64_t rows_per_slice,
-                                                            uint64_t* __restrict__ parts, int32_t* __restrict__ err) {
+                                                            uint64_t* __restrict__ parts, int32_t* __restrict__ err, int64_t qb) {
   using T = typename ScanElem<E>::T;
   constexpr bool kTwo = ScanElem<E>::kTerms == 2;
-  constexpr int kBTerms = 2;
+  constexpr int kBTerms = SELF ? ScanElem<E>::kTerms : 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char scan_lds[];
   u32x4* bl = reinterpret_cast<u32x4*>(scan_lds);
   uint64_t* items = reinterpret_cast<uint64_t*>(scan_lds + kScanChunkBytes);
@@ -299,7 +316,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
   const int nchunks = (dim + kScanKChunk - 1) / kScanKChunk;
   const int64_t row_begin = (int64_t)slice * rows_per_slice;
   const int64_t row_end = min(m, row_begin + rows_per_slice);
-  const u32x4* bimg = image + (int64_t)qtile * nchunks * (kScanChunkBytes / 16);
+  const u32x4* bimg = image + (int64_t)qtile * nchunks * (kBTerms * 512);
 
   if (tid < kScanQTile) {
     thr[tid] = 0ull;
@@ -311,6 +328,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
   for (int cb = 0; cb < 2; ++cb) {
     const int qi = qtile * kScanQTile + cb * 32 + r;
     qok[cb] = qi < q;
+    if constexpr (SELF) qok[cb] = qok[cb] && (row_ids == nullptr || row_ids[qb + qi] >= 0);
     qn[cb] = qnorm[qi];                   // (padded to whole tiles)
   }
   __syncthreads();
@@ -335,6 +353,12 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
         const uint32_t rowlo = 0xffffffffu - (uint32_t)(row0[t] + 4 * h);
         uint32_t pend = 0;
         uint64_t bar = thr[qc];
+        // SELF: the offset in this tile of the lane's own query row (qb + qtile * 64 + cb * 32 + r), -1 where it is not in it
+        int own = -1;
+        if constexpr (SELF) {
+          const int64_t ahead = qb + (int64_t)qtile * kScanQTile + cb * 32 - row0[t];     // (uniform)
+          own = (ahead < -32 || ahead > 32) ? -1 : (int)ahead + r;
+        }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int rr = (i & 3) + 8 * (i >> 2) + 4 * h;
@@ -342,7 +366,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void scan_kernel(const typename Sc
           const float sc = acc[t][cb][i] / (rn * qn[cb]);
           acc[t][cb][i] = sc;
           const uint64_t it = key_item(asc_key(sc), rowlo - (uint32_t)((i & 3) + 8 * (i >> 2)));
-          if (qok[cb] && ((livemask >> rr) & 1u) && sc == sc && it > bar) pend |= 1u << i;
+          if (qok[cb] && ((livemask >> rr) & 1u) && (!SELF || rr != own) && sc == sc && it > bar) pend |= 1u << i;
         }
         for (;;) {
 #pragma unroll
@@ -678,14 +702,22 @@ inline int scan_geometry(int32_t q, int64_t m, int32_t dim, ScanPlan& p) {
   return bad ? bad : scan_front_bytes((q + kScanQTile - 1) / kScanQTile, p);
 }
 
-inline int scan_plan(int32_t q, int64_t m, int32_t dim, int32_t window, ScanPlan& p) {
+// the selection's window -> the per-query buffer (p.cap), and the LDS of a scan_kernel workgroup with it
+inline int scan_window_cap(int32_t window, ScanPlan& p) {
   if (window <= 0 || window > kScanMaxWindow) return LSHRS_E_BADARG;
-  const int bad = scan_geometry(q, m, dim, p);
-  if (bad) return bad;
   p.cap = 64;
   while (p.cap < 2 * window) p.cap <<= 1;
-  const int64_t lds = (int64_t)kScanChunkBytes + (int64_t)kScanQTile * p.cap * 8 + kScanQTile * 12;
-  scan_slices(m, p.qtiles, lds, kScanMergeItems / window, p.rows_per_slice, p.slices);
+  return 0;
+}
+
+inline int64_t scan_select_lds(int cap) { return (int64_t)kScanChunkBytes + (int64_t)kScanQTile * cap * 8 + kScanQTile * 12; }
+
+inline int scan_plan(int32_t q, int64_t m, int32_t dim, int32_t window, ScanPlan& p) {
+  int bad = scan_window_cap(window, p);
+  if (bad) return bad;
+  bad = scan_geometry(q, m, dim, p);
+  if (bad) return bad;
+  scan_slices(m, p.qtiles, scan_select_lds(p.cap), kScanMergeItems / window, p.rows_per_slice, p.slices);
   p.parts_bytes = (int64_t)q * p.slices * window * (int64_t)sizeof(uint64_t);
   return 0;
 }
@@ -723,7 +755,41 @@ inline int scan_pairs_plan(int64_t m, int32_t dim, int32_t qblock, ScanPlan& p) 
   return scan_front_bytes(tiles, p);
 }
 
-// the front of all three entries: the image and the norms at the head of the workspace, written by scan_image_kernel and
+// k-NN self-join: the rows [q_begin, q_begin + q_count) as queries in blocks as the self-join plans them, the range in place of
+// the rows (scan_pairs_plan of q_count rows; a caller's block is taken as it is).  Every block scans all m rows in slices of
+// its own (scan_knn_block); the slices' winners of the workspace are those of the block that has most: the first - a full one,
+// or the only one - or the last, which has fewer rows and may have more slices.
+inline void scan_knn_block(int64_t m, int32_t qn, int32_t window, ScanPlan& p) {
+  p.qtiles = (qn + kScanQTile - 1) / kScanQTile;
+  scan_slices(m, p.qtiles, scan_select_lds(p.cap), kScanMergeItems / window, p.rows_per_slice, p.slices, kScanKnnPerCu);
+  p.parts_bytes = (int64_t)qn * p.slices * window * (int64_t)sizeof(uint64_t);
+}
+
+inline int scan_knn_plan(int32_t q_count, int64_t m, int32_t dim, int32_t window, int32_t qblock, ScanPlan& p) {
+  if (q_count < 0 || q_count > m) return LSHRS_E_BADARG;
+  int bad = scan_window_cap(window, p);
+  if (bad) return bad;
+  const int cap = p.cap;
+  bad = scan_pairs_plan(q_count > 0 ? q_count : 1, dim, qblock, p);
+  if (bad) return bad;
+  bad = scan_rows_geometry(m, dim, p);
+  if (bad) return bad;
+  p.cap = cap;
+  const int block_tiles = p.qtiles;
+  const int64_t block_rows = (int64_t)block_tiles * kScanQTile;
+  const int32_t first = (int32_t)(q_count < block_rows ? q_count : block_rows), last = (int32_t)(q_count % block_rows);
+  int64_t parts = 0;
+  for (const int32_t qn : {first, last})
+    if (qn > 0) {
+      scan_knn_block(m, qn, window, p);
+      if (p.parts_bytes > parts) parts = p.parts_bytes;
+    }
+  p.qtiles = block_tiles;           // (image_bytes and qnorm_bytes are the block's: scan_front_bytes)
+  p.parts_bytes = parts;
+  return 0;
+}
+
+// the front of all four entries: the image and the norms at the head of the workspace, written by scan_image_kernel and
 // scan_norm_kernel from `qn` queries - rows of Q at `qsrc` (stride qld), those from qb on, the dead ones by `qrow_ids` left
 // out: f32 queries, or a block of the corpus itself - and whether the corpus takes the ALIGNED instantiation (16-byte vector
 // loads of whole chunks).  p.qtiles covers qn; p.image_bytes may be a larger block's.
@@ -770,18 +836,41 @@ int scan_emit_begin(const void* corpus, int64_t ldc, int32_t dim, int64_t capaci
   return e != hipSuccess ? -(int)e : 0;
 }
 
-template <typename E, bool ALIGNED>
+// the selection of one launch, for both kinds of query: scan_kernel over the plan's grid - SELF: the queries are the rows
+// [qb, qb + q) - then scan_merge_kernel of the slices' winners into the caller's arrays
+template <typename E, bool ALIGNED, bool SELF>
 int scan_launch(const ScanPlan& p, const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim,
                 const int64_t* row_ids, const u32x4* image, const float* qnorm, int32_t q, int32_t window, uint64_t* parts,
-                int32_t* err, hipStream_t s) {
-  const size_t shmem = (size_t)kScanChunkBytes + (size_t)kScanQTile * p.cap * 8 + kScanQTile * 8 + kScanQTile * 4;
+                int32_t* err, int64_t qb, hipStream_t s) {
+  const size_t shmem = (size_t)scan_select_lds(p.cap);
   if (shmem > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(scan_kernel<E, ALIGNED>),
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(scan_kernel<E, ALIGNED, SELF>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e != hipSuccess) return -(int)e;
   }
-  hipLaunchKernelGGL((scan_kernel<E, ALIGNED>), dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(kScanThreads), shmem, s, corpus,
-                     m, ldc, dim, row_ids, image, qnorm, q, window, p.cap, p.rows_per_slice, parts, err);
+  hipLaunchKernelGGL((scan_kernel<E, ALIGNED, SELF>), dim3((unsigned)p.slices, (unsigned)p.qtiles), dim3(kScanThreads), shmem, s,
+                     corpus, m, ldc, dim, row_ids, image, qnorm, q, window, p.cap, p.rows_per_slice, parts, err, qb);
+  return -(int)hipGetLastError();
+}
+
+template <typename E, bool SELF>
+int scan_select(const ScanPlan& p, const ScanFront& f, const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim,
+                const int64_t* row_ids, int32_t q, int32_t window, uint64_t* parts, int64_t* out_rows, float* out_approx,
+                int32_t* out_count, int32_t* err, int64_t qb, hipStream_t s) {
+  const int rc = f.aligned ? scan_launch<E, true, SELF>(p, corpus, m, ldc, dim, row_ids, f.image, f.qnorm, q, window, parts, err, qb, s)
+                           : scan_launch<E, false, SELF>(p, corpus, m, ldc, dim, row_ids, f.image, f.qnorm, q, window, parts, err, qb, s);
+  if (rc) return rc;
+  const int n = p.slices * window;
+  int npad = 2;
+  while (npad < n) npad <<= 1;
+  const size_t merge_lds = (size_t)npad * sizeof(uint64_t);
+  if (merge_lds > 48 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(scan_merge_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)merge_lds);
+    if (e != hipSuccess) return -(int)e;
+  }
+  hipLaunchKernelGGL(scan_merge_kernel, dim3((unsigned)q), dim3(kScanThreads), merge_lds, s, parts, n, npad, window, out_rows,
+                     out_approx, out_count);
   return -(int)hipGetLastError();
 }
 
@@ -799,21 +888,37 @@ int scan_topk(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int
   hipStream_t s = static_cast<hipStream_t>(stream);
   uint64_t* parts = reinterpret_cast<uint64_t*>(static_cast<unsigned char*>(workspace) + p.image_bytes + p.qnorm_bytes);
   const ScanFront f = scan_front<E>(p, corpus, ldc, dim, queries, q, workspace, err, s);
-  const int rc = f.aligned ? scan_launch<E, true>(p, corpus, m, ldc, dim, row_ids, f.image, f.qnorm, q, window, parts, err, s)
-                           : scan_launch<E, false>(p, corpus, m, ldc, dim, row_ids, f.image, f.qnorm, q, window, parts, err, s);
-  if (rc) return rc;
-  const int n = p.slices * window;
-  int npad = 2;
-  while (npad < n) npad <<= 1;
-  const size_t merge_lds = (size_t)npad * sizeof(uint64_t);
-  if (merge_lds > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(scan_merge_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)merge_lds);
-    if (e != hipSuccess) return -(int)e;
+  return scan_select<E, false>(p, f, corpus, m, ldc, dim, row_ids, q, window, parts, out_rows, out_approx, out_count, err, 0, s);
+}
+
+// k-NN self-join: the rows [q_begin, q_begin + q_count) as queries, a block at a time, one after the other on the stream; the
+// blocks share the workspace (image | norms | the slices' winners) and each merges into the caller's arrays at its offset
+template <typename E>
+int scan_knn(const typename ScanElem<E>::T* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, int64_t q_begin,
+             int32_t q_count, int32_t window, int32_t qblock, int64_t* out_rows, float* out_approx, int32_t* out_count,
+             void* workspace, int32_t* err, void* stream) {
+  ScanPlan p;
+  const int bad = scan_knn_plan(q_count, m, dim, window, qblock, p);
+  if (bad) return bad;
+  const auto addr = [](const void* ptr) { return reinterpret_cast<uintptr_t>(ptr); };
+  if (q_begin < 0 || q_begin > m - q_count || (addr(row_ids) & 7) || (addr(out_rows) & 7) || (addr(out_approx) & 3) ||
+      (addr(out_count) & 3) || (addr(workspace) & 15) || (addr(err) & 3))
+    return LSHRS_E_BADARG;
+  if (q_count == 0) return 0;
+  if (corpus == nullptr || out_rows == nullptr || out_approx == nullptr || out_count == nullptr || workspace == nullptr || ldc < dim)
+    return LSHRS_E_BADARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint64_t* parts = reinterpret_cast<uint64_t*>(static_cast<unsigned char*>(workspace) + p.image_bytes + p.qnorm_bytes);
+  const int64_t block_rows = (int64_t)p.qtiles * kScanQTile;
+  for (int64_t done = 0; done < q_count; done += block_rows) {
+    const int qn = (int)(q_count - done < block_rows ? q_count - done : block_rows);
+    scan_knn_block(m, qn, window, p);
+    const ScanFront f = scan_front<E, E>(p, corpus, ldc, dim, corpus, ldc, row_ids, q_begin + done, qn, workspace, err, s);
+    const int rc = scan_select<E, true>(p, f, corpus, m, ldc, dim, row_ids, qn, window, parts, out_rows + done * window,
+                                        out_approx + done * window, out_count + done, err, q_begin + done, s);
+    if (rc) return rc;
   }
-  hipLaunchKernelGGL(scan_merge_kernel, dim3((unsigned)q), dim3(kScanThreads), merge_lds, s, parts, n, npad, window, out_rows,
-                     out_approx, out_count);
-  return -(int)hipGetLastError();
+  return 0;
 }
 
 template <typename E>
@@ -1009,6 +1114,48 @@ int lshrs_scan_pairs_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32
                           void* workspace, int32_t* err, void* stream) {
   return scan_pairs<F8E4M3>(corpus, m, ldc, dim, row_ids, bar, qblock, capacity, out_a, out_b, out_approx, total, workspace, err,
                          stream);
+}
+
+int64_t lshrs_scan_knn_workspace_bytes(int32_t q_count, int64_t m, int32_t dim, int32_t window, int32_t qblock) {
+  ScanPlan p;
+  const int bad = scan_knn_plan(q_count, m, dim, window, qblock, p);
+  if (bad) return bad;
+  return p.image_bytes + p.qnorm_bytes + p.parts_bytes + 16;
+}
+
+int lshrs_scan_knn_f32(const float* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, int64_t q_begin,
+                       int32_t q_count, int32_t window, int32_t qblock, int64_t* out_rows, float* out_approx, int32_t* out_count,
+                       void* workspace, int32_t* err, void* stream) {
+  return scan_knn<float>(corpus, m, ldc, dim, row_ids, q_begin, q_count, window, qblock, out_rows, out_approx, out_count, workspace,
+                       err, stream);
+}
+
+int lshrs_scan_knn_bf16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, int64_t q_begin,
+                       int32_t q_count, int32_t window, int32_t qblock, int64_t* out_rows, float* out_approx, int32_t* out_count,
+                       void* workspace, int32_t* err, void* stream) {
+  return scan_knn<Bf16>(corpus, m, ldc, dim, row_ids, q_begin, q_count, window, qblock, out_rows, out_approx, out_count, workspace,
+                       err, stream);
+}
+
+int lshrs_scan_knn_f16(const uint16_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, int64_t q_begin,
+                       int32_t q_count, int32_t window, int32_t qblock, int64_t* out_rows, float* out_approx, int32_t* out_count,
+                       void* workspace, int32_t* err, void* stream) {
+  return scan_knn<F16>(corpus, m, ldc, dim, row_ids, q_begin, q_count, window, qblock, out_rows, out_approx, out_count, workspace,
+                       err, stream);
+}
+
+int lshrs_scan_knn_i8(const int8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, int64_t q_begin,
+                       int32_t q_count, int32_t window, int32_t qblock, int64_t* out_rows, float* out_approx, int32_t* out_count,
+                       void* workspace, int32_t* err, void* stream) {
+  return scan_knn<I8>(corpus, m, ldc, dim, row_ids, q_begin, q_count, window, qblock, out_rows, out_approx, out_count, workspace,
+                       err, stream);
+}
+
+int lshrs_scan_knn_f8e4m3(const uint8_t* corpus, int64_t m, int64_t ldc, int32_t dim, const int64_t* row_ids, int64_t q_begin,
+                       int32_t q_count, int32_t window, int32_t qblock, int64_t* out_rows, float* out_approx, int32_t* out_count,
+                       void* workspace, int32_t* err, void* stream) {
+  return scan_knn<F8E4M3>(corpus, m, ldc, dim, row_ids, q_begin, q_count, window, qblock, out_rows, out_approx, out_count, workspace,
+                       err, stream);
 }
 
 }  // extern "C"

@@ -386,6 +386,20 @@ class DeviceVectors:
         self.last_search_stats = stats
         return got
 
+    def neighbors(self, k: int = 10, *, method: str = "auto", return_tensors: bool = False):
+        """The ``k`` OTHER stored vectors nearest to every stored vector by cosine, exactly, under the caller's ids - the k-NN
+        graph of the store: ``(ids (n,) int64 ascending, neighbors (n, kk) int64, scores (n, kk) float32)``, ``kk = min(k,
+        len(self) - 1)`` - :func:`lshrs_amd.exact_knn` over the row block where it is, superseded and erased rows left out.
+        What the call did (rows, live rows, rows settled by the first pass, rows gathered, window, epsilon, chunks) is left in
+        ``last_search_stats``."""
+        from ._exact import exact_knn
+
+        rows, row_ids = self._search_snapshot()
+        stats: Dict[str, Any] = {}
+        got = exact_knn(rows, k, row_ids=row_ids, method=method, return_tensors=return_tensors, stats=stats)
+        self.last_search_stats = stats
+        return got
+
     def _search(self, fn, queries, what, **kwargs):
         """``fn`` (``exact_top_k`` / ``exact_above``) of ``queries`` and ``what`` (its ``k`` / ``threshold``) over one snapshot
         of the row block and its row -> id list; what it did goes to ``last_search_stats``."""
