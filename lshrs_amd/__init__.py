@@ -12,6 +12,7 @@ compute call raises ``lshrs_amd._native.NativeLibraryError``.
 
 from ._config import HashSignatures
 from ._exact import exact_above, exact_knn, exact_pairs_above, exact_top_k, scan_epsilon, scan_max_window
+from ._join import lsh_pairs_above
 from ._native import NativeLibraryError
 from .bandrows import get_optimal_config
 from .core import LSHRS, lshrs
@@ -23,7 +24,7 @@ from .vectors import DeviceVectors
 
 __all__ = [
     "LSHRS", "lshrs", "LSHHasher", "HashSignatures", "top_k_cosine", "cosine_similarity", "l2_norm",
-    "rerank_batch", "quantize_rows", "exact_top_k", "exact_above", "exact_pairs_above", "exact_knn", "scan_epsilon", "scan_max_window",
+    "rerank_batch", "quantize_rows", "exact_top_k", "exact_above", "exact_pairs_above", "exact_knn", "lsh_pairs_above", "scan_epsilon", "scan_max_window",
     "get_optimal_config", "InMemoryStorage", "BucketOperation", "NativeLibraryError",
     "RedisPackedWriter", "group_by_bucket", "hex_keys", "HostBlasNotRecognised",
     "DeviceVectors",

@@ -21,7 +21,8 @@ rerank_rounding)``, which no row of the answer can lie below, and the rerank's k
 
 ``exact_pairs_above`` is the self-join on that pass (``lshrs_scan_pairs_*``): every pair of live rows whose rerank score reaches
 a threshold - the stored rows are their own queries, every unordered pair is multiplied once, and the rerank's kernel judges what
-the pass lets through, the row of the lower id as the query.
+the pass lets through, the row of the lower id as the query (``_judge_pairs``: the text the LSH self-join of ``_join.py`` judges
+its buckets' pairs with, too).
 
 ``exact_knn`` is the k-NN self-join on the top-k pass (``lshrs_scan_knn_*``): for every live row the ``k`` OTHER live rows
 nearest to it - the stored rows are their own queries, a block at a time, no row enters its own window, and the settle rule and
@@ -41,7 +42,7 @@ from .similarity import (_CORPUS_ENTRY, _CORPUS_ENTRY_8BIT, _on_device, _raise_f
                          cosine_scores_device, topk_desc_device)
 
 __all__ = ["exact_top_k", "exact_above", "exact_pairs_above", "exact_knn", "scan_knn", "settled", "choose_window", "rerank_rounding", "scan_epsilon",
-           "scan_max_window", "scan_windows", "scan_above", "scan_pairs", "above_bars", "above_recall"]
+           "scan_max_window", "scan_windows", "scan_above", "scan_pairs", "above_bars", "above_recall", "collision_law"]
 
 METHODS = ("auto", "scan", "gather")
 # (query, live row) pairs of one chunk of the gather.  Per pair: 4 B of score, 8 B of candidate row, 1 B of status, and up to
@@ -508,6 +509,51 @@ def _check_pairs_args(threshold, max_pairs) -> float:
     return float(_check_above_args(1, float(t), max_pairs)[0])
 
 
+def _judge_pairs(torch, corpus, d_ids, pa, pb, t32: float):
+    """What a self-join does with the pairs of row positions ``(pa, pb)`` its first pass let through - the exhaustive pass of
+    ``exact_pairs_above``, the buckets of ``lsh_pairs_above``: oriented by id, rescored by the rerank's kernel, cut at
+    ``t32`` (the threshold as a float32) and ordered.  Returns ``(ids_a, ids_b, scores, index)``: ``ids_a < ids_b``, scores
+    descending, equal scores by ascending ``(ids_a, ids_b)``; ``index`` (int64): for every pair of the answer its position in
+    ``pa`` / ``pb``, so that whatever else the caller holds per pair can follow."""
+    dev = corpus.device
+    n, dim = int(pa.shape[0]), int(corpus.shape[1])
+    index = torch.arange(n, dtype=torch.int64, device=dev)
+    # the orientation is by id: the row of the lower id asks, the row of the higher id is scored
+    if d_ids is not None:
+        ia, ib = d_ids[pa], d_ids[pb]
+        swap = ia > ib
+        pa, pb = torch.where(swap, pb, pa), torch.where(swap, pa, pb)
+        ia, ib = torch.where(swap, ib, ia), torch.where(swap, ia, ib)
+    else:
+        ia, ib = pa, pb
+    # by asking row (stable): its pairs are one ragged list; the distinct asking rows a chunk at a time as queries
+    pa, by_a = torch.sort(pa, stable=True)
+    pb, ia, ib, index = pb[by_a].contiguous(), ia[by_a], ib[by_a], index[by_a]
+    urows, count = torch.unique_consecutive(pa, return_counts=True)
+    off = (torch.cumsum(count, 0) - count).contiguous()
+    count32 = count.to(torch.int32)
+    exact = torch.empty((n,), dtype=torch.float32, device=dev)
+    err2 = torch.zeros(1, dtype=torch.int32, device=dev)
+    step = max(1, _PAIRS_QUERY_BYTES // (4 * dim))
+    for lo in range(0, int(urows.shape[0]), step):
+        hi = min(int(urows.shape[0]), lo + step)
+        queries = _rows_as_f32(torch, corpus, urows[lo:hi])
+        cosine_ragged_device(corpus, queries, pb, off[lo:hi].contiguous(), count32[lo:hi].contiguous(), n,
+                             scores=exact, err=err2)
+    if int(err2.item()) & 5:
+        raise ValueError("Cannot normalize zero vector")
+    keep = exact >= t32                     # (a NaN is not kept)
+    ia, ib, exact, index = ia[keep], ib[keep], exact[keep], index[keep]
+    # ascending (ids_a, ids_b) by two stable sorts, then ONE stable sort on an integer that descends with the score
+    # (-0.0 with 0.0): descending score, ties in the id order
+    _, order = torch.sort(ib, stable=True)
+    ia, ib, exact, index = ia[order], ib[order], exact[order], index[order]
+    _, order = torch.sort(ia, stable=True)
+    ia, ib, exact, index = ia[order], ib[order], exact[order], index[order]
+    _, order = torch.sort(_descending(torch, exact), stable=True)
+    return ia[order].contiguous(), ib[order].contiguous(), exact[order].contiguous(), index[order].contiguous()
+
+
 def exact_pairs_above(corpus, threshold, *, row_ids=None, max_pairs: int = 1 << 26, return_tensors: bool = False,
                       stats: Optional[Dict] = None):
     """Every pair of rows of ``corpus`` at or above a cosine ``threshold``, exactly - the near-duplicates among the stored
@@ -555,41 +601,7 @@ def exact_pairs_above(corpus, threshold, *, row_ids=None, max_pairs: int = 1 << 
             pa, pb, emitted = _all_pairs(lambda cap: scan_pairs(corpus, bar, cap, d_ids), capacity, max_pairs,
                                          "exact_pairs_above", out)
             if emitted:
-                pa, pb = pa[:emitted], pb[:emitted]
-                # the orientation is by id: the row of the lower id asks, the row of the higher id is scored
-                if d_ids is not None:
-                    ia, ib = d_ids[pa], d_ids[pb]
-                    swap = ia > ib
-                    pa, pb = torch.where(swap, pb, pa), torch.where(swap, pa, pb)
-                    ia, ib = torch.where(swap, ib, ia), torch.where(swap, ia, ib)
-                else:
-                    ia, ib = pa, pb
-                # by asking row (stable): its pairs are one ragged list; the distinct asking rows a chunk at a time as queries
-                pa, by_a = torch.sort(pa, stable=True)
-                pb, ia, ib = pb[by_a].contiguous(), ia[by_a], ib[by_a]
-                urows, count = torch.unique_consecutive(pa, return_counts=True)
-                off = (torch.cumsum(count, 0) - count).contiguous()
-                count32 = count.to(torch.int32)
-                exact = torch.empty((emitted,), dtype=torch.float32, device=dev)
-                err2 = torch.zeros(1, dtype=torch.int32, device=dev)
-                step = max(1, _PAIRS_QUERY_BYTES // (4 * dim))
-                for lo in range(0, int(urows.shape[0]), step):
-                    hi = min(int(urows.shape[0]), lo + step)
-                    queries = _rows_as_f32(torch, corpus, urows[lo:hi])
-                    cosine_ragged_device(corpus, queries, pb, off[lo:hi].contiguous(), count32[lo:hi].contiguous(), emitted,
-                                         scores=exact, err=err2)
-                if int(err2.item()) & 5:
-                    raise ValueError("Cannot normalize zero vector")
-                keep = exact >= t32                     # (a NaN is not kept)
-                ia, ib, exact = ia[keep], ib[keep], exact[keep]
-                # ascending (ids_a, ids_b) by two stable sorts, then ONE stable sort on an integer that descends with the score
-                # (-0.0 with 0.0): descending score, ties in the id order
-                _, order = torch.sort(ib, stable=True)
-                ia, ib, exact = ia[order], ib[order], exact[order]
-                _, order = torch.sort(ia, stable=True)
-                ia, ib, exact = ia[order], ib[order], exact[order]
-                _, order = torch.sort(_descending(torch, exact), stable=True)
-                ids_a, ids_b, scores = ia[order].contiguous(), ib[order].contiguous(), exact[order].contiguous()
+                ids_a, ids_b, scores, _ = _judge_pairs(torch, corpus, d_ids, pa[:emitted], pb[:emitted], t32)
                 out["kept"] = int(ids_a.shape[0])
     return _finish(stats, out, (ids_a, ids_b, scores), return_tensors)
 
@@ -739,6 +751,17 @@ def exact_knn(corpus, k: int, *, row_ids=None, method: str = "auto", return_tens
     return _finish(stats, out, (live_ids, neighbors, scores), return_tensors)
 
 
+def collision_law(scores, num_bands: int, rows_per_band: int) -> float:
+    """The mean over pairs of cosine ``scores`` of ``1 - (1 - p^r)^b`` with ``p = 1 - acos(s) / pi``: the chance that sign
+    random projections put such a pair into one bucket of at least one of ``b = num_bands`` bands of ``r = rows_per_band``
+    bits (NaN when there is no pair).  What ``above_recall`` and ``LSHRS.recall_pairs_above`` report as ``expected``."""
+    scores = np.asarray(scores, dtype=np.float64)
+    if not scores.shape[0]:
+        return float("nan")
+    p = 1.0 - np.arccos(np.clip(scores, -1.0, 1.0)) / np.pi
+    return float(np.mean(1.0 - (1.0 - p ** int(rows_per_band)) ** int(num_bands)))
+
+
 def above_recall(truth_ids, truth_scores, truth_bounds, cand_ids, cand_bounds, num_bands: int, rows_per_band: int) -> Dict:
     """The bookkeeping of ``LSHRS.recall_above``, on host arrays: the truth (ids, scores, bounds of :func:`exact_above`) against
     candidate lists (ids, bounds; every id at most once per query).  Returns ``recall`` (truth pairs that are candidates /
@@ -764,10 +787,7 @@ def above_recall(truth_ids, truth_scores, truth_bounds, cand_ids, cand_bounds, n
             found += hit
             per[i] = hit / mine.shape[0]
     truth_pairs, cand_pairs = int(truth_ids.shape[0]), int(cand_ids.shape[0])
-    expected = float("nan")
-    if truth_pairs:
-        p = 1.0 - np.arccos(np.clip(truth_scores, -1.0, 1.0)) / np.pi
-        expected = float(np.mean(1.0 - (1.0 - p ** int(rows_per_band)) ** int(num_bands)))
+    expected = collision_law(truth_scores, num_bands, rows_per_band)
     return {"recall": found / truth_pairs if truth_pairs else 1.0, "per_query": per, "truth_pairs": truth_pairs,
             "candidates": cand_pairs / n if n else 0.0, "precision": found / cand_pairs if cand_pairs else 1.0,
             "expected": expected}

@@ -1,4 +1,5 @@
-"""ctypes binding of ``csrc/liblshrs_hip.so`` (the C ABI declared in ``include/lshrs_hip.h`` and ``include/lshrs_knn.h``).
+"""ctypes binding of ``csrc/liblshrs_hip.so`` (the C ABI declared in ``include/lshrs_hip.h``, ``include/lshrs_knn.h`` and
+``include/lshrs_join.h``).
 
 There is no CPU implementation behind this module: if the shared library has not
 been built, or the ABI version does not match, loading raises — loudly — and so
@@ -18,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 # one translation unit per kernel family (what they share: csrc/lshrs_common.h); pipeline.hip: the native driver of the host-engine route
-UNITS = ("sig_setup", "sig_f32", "sig16", "sig16r", "sig_replay", "sig_small", "sig_split", "storage", "rerank", "query", "idmap", "scan", "pipeline")
+UNITS = ("sig_setup", "sig_f32", "sig16", "sig16r", "sig_replay", "sig_small", "sig_split", "storage", "rerank", "query", "idmap", "scan", "pipeline", "join")
 SOURCES = tuple(os.path.join(CSRC, u + ".hip") for u in UNITS)
 SOURCE = SOURCES[0]
 # (LSHRS_HIP_LIBRARY: load another build of the same ABI instead - A/B measurements of compiler flags, tools/ab_build.py)
@@ -255,6 +256,16 @@ def _declare(lib: ctypes.CDLL) -> None:
     for dt in SCAN_ELEMS:
         knn = getattr(lib, "lshrs_scan_knn_" + dt)
         knn.argtypes, knn.restype = [vp, i64, i64, i32, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp], c.c_int
+    # the LSH self-join (include/lshrs_join.h): (n_rows, num_bands)
+    lib.lshrs_join_workspace_bytes.argtypes = [i64, i32]
+    lib.lshrs_join_workspace_bytes.restype = i64
+    # (codes, offsets, n_codes, band_bytes, num_bands, member_rows, n_members, n_rows, max_bucket, workspace, err, stream)
+    lib.lshrs_join_rowmap_i64.argtypes = [vp, vp, i64, i32, i32, vp, i64, i64, i64, vp, vp, vp]
+    lib.lshrs_join_rowmap_i64.restype = c.c_int
+    # (offsets, pair_prefix, n_codes, member_rows, n_rows, num_bands, workspace, raw_begin, raw_count, min_collisions, capacity,
+    #  out_a, out_b, out_hits, total, stream)
+    lib.lshrs_join_emit_i64.argtypes = [vp, vp, i64, vp, i64, i32, vp, i64, i64, i32, i64, vp, vp, vp, vp, vp]
+    lib.lshrs_join_emit_i64.restype = c.c_int
     lib.lshrs_pipe_create.argtypes = [i32, i32, i32, i32, i32]
     lib.lshrs_pipe_create.restype = vp
     lib.lshrs_pipe_destroy.argtypes = [vp]
@@ -348,6 +359,12 @@ EXPORTS_KNN = (
     "lshrs_scan_knn_i8",
     "lshrs_scan_knn_f8e4m3",
 )
+# ... and include/lshrs_join.h (additive to ABI 7 as well)
+EXPORTS_JOIN = (
+    "lshrs_join_workspace_bytes",
+    "lshrs_join_rowmap_i64",
+    "lshrs_join_emit_i64",
+)
 
 
 def load() -> ctypes.CDLL:
@@ -372,7 +389,7 @@ def load() -> ctypes.CDLL:
             lib = ctypes.CDLL(LIBRARY)
         except OSError as exc:  # pragma: no cover - environment specific
             raise NativeLibraryError(f"cannot load {LIBRARY}: {exc}") from exc
-        for name in EXPORTS + EXPORTS_KNN:
+        for name in EXPORTS + EXPORTS_KNN + EXPORTS_JOIN:
             if not hasattr(lib, name):
                 raise NativeLibraryError(f"{LIBRARY} does not export {name}; rebuild it")
         _declare(lib)

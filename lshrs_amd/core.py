@@ -215,6 +215,7 @@ class LSHRS:
         self._dev_buckets = DeviceBuckets()  # device mirror of the store's bucket arrays (query_many)
         self._one_query: Dict[int, Any] = {}    # per device: the pinned / device buffers of the single-query chain
         self._one_table = None          # the store's segments as a device table, beside the token of their snapshot (_bucket_table)
+        self._one_join = None           # ... and as ONE folded segment on the device, for the self-join (_join_segment)
         self._config: Dict[str, Any] = {
             "dim": dim, "num_perm": num_perm, "num_bands": num_bands, "rows_per_band": rows_per_band,
             "similarity_threshold": similarity_threshold, "buffer_size": buffer_size, "seed": seed,
@@ -732,6 +733,102 @@ class LSHRS:
         cand_ids, _, cand_bounds = self.query_many(vectors, top_k=None, return_arrays=True)
         return above_recall(t_ids, t_scores, t_bounds, cand_ids, cand_bounds, self._config["num_bands"],
                             self._config["rows_per_band"])
+
+    def pairs_above(self, threshold, *, min_collisions: int = 1, max_bucket: Optional[int] = None, max_pairs: int = 1 << 26,
+                    return_arrays: bool = False):
+        """The near-duplicate pairs the index holds IN ITS BUCKETS at or above a cosine ``threshold`` (one number): the LSH
+        self-join, the approximate counterpart of :meth:`pairs_exact_above` (``lshrs_amd.lsh_pairs_above``).  Two ids are a
+        candidate pair when they share a bucket in at least ``min_collisions`` bands (an integer of ``1 .. num_bands``);
+        buckets of more than ``max_bucket`` members (None: no limit; else ``>= 2``) count in no role - neither as a source
+        of pairs nor as a collision.  Every candidate pair is reranked once, the vector of the lower id as the query, and kept
+        when its score reaches ``float32(threshold)``: for ``min_collisions = 1`` and no ``max_bucket`` the answer is
+        :meth:`pairs_exact_above` restricted to the candidate pairs, scores bit for bit.  Returns ``[(id_a, id_b, score,
+        collisions), ...]`` with ``id_a < id_b``, scores descending and equal scores by ascending ``(id_a, id_b)`` - or the four
+        arrays with ``return_arrays``.  Nothing is hashed: the pairs come out of the bucket arrays as they stand.
+
+        The store must keep every bucket as arrays (``packed_ingest``; no op-tuple buckets, keys of at most 6 bytes, not
+        Redis), else ``RuntimeError``: there is no host fallback.  Several array segments are folded into one on the host
+        (``packed_ops.merge_csr``: an id once per bucket) and the folded segment is kept on the device beside the store's
+        snapshot token, so that a second call folds nothing; ``last_search_stats["fold_ms"]`` says what this call's fold cost.
+        An id that sits in two different buckets of one band - indexed under two signatures and never deleted - raises
+        ``ValueError`` before any pair is emitted; an id in the buckets without a vector raises ``IndexError``.  The vectors and
+        the buckets are two snapshots taken one after the other, without a lock across both: an ``index()`` that lands between
+        them can surface as that ``IndexError``.  Without a corpus or a store the call raises what :meth:`pairs_exact_above`
+        raises; an empty index gives an empty answer.  ``last_search_stats`` receives ``buckets``, ``skipped_buckets``,
+        ``raw_pairs`` (pairs the counted buckets hold, with repetitions), ``emitted`` (distinct candidate pairs), ``kept``,
+        ``launches`` (emit launches), ``segments_folded`` and ``fold_ms``."""
+        from . import _join
+
+        nb, bb = int(self._config["num_bands"]), int(self._hasher.band_bytes)
+        _join.check_join_args(threshold, min_collisions, max_bucket, max_pairs, nb)
+        kw = {"min_collisions": int(min_collisions), "max_bucket": max_bucket, "max_pairs": int(max_pairs)}
+        fold: Dict[str, Any] = {}
+        empty = (np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.float32), np.empty(0, np.int32))
+
+        def in_store(store, _, t):
+            seg = self._join_segment(store.snapshot()[0].device, bb, fold)
+            return empty if seg is None else store.lsh_pairs_above(t, *seg, nb, bb, **kw)
+
+        def in_tensor(_, table, t, stats):
+            seg = self._join_segment(table.device, bb, fold)        # (the id is the row)
+            return empty if seg is None else _join.lsh_pairs_above(table, t, *seg, nb, bb, stats=stats, **kw)
+
+        ids_a, ids_b, scores, collisions = self._search_corpus("pairs_above", in_store, in_tensor, None, threshold)
+        if fold.pop("empty"):
+            self.last_search_stats = {"buckets": 0, "skipped_buckets": 0, "raw_pairs": 0, "emitted": 0, "kept": 0, "launches": 0}
+        self.last_search_stats.update(fold)
+        if return_arrays:
+            return ids_a, ids_b, scores, collisions
+        with _gc_paused():
+            return list(zip(ids_a.tolist(), ids_b.tolist(), scores.astype(np.float64).tolist(), collisions.tolist()))
+
+    def _join_segment(self, dev, band_bytes: int, fold: Dict[str, Any]):
+        """The store's bucket arrays as ONE segment on ``dev`` - ``(codes, offsets, members)`` int64 tensors, None for an empty
+        index - folded where the store holds several (``_join.fold_segments``) and kept beside the token that came back with the
+        segments, as :meth:`_bucket_table` keeps its table.  ``fold`` receives ``segments_folded``, ``fold_ms`` (both 0 where
+        the kept segment served) and ``empty``.  A store that does not keep every bucket as arrays raises ``RuntimeError``."""
+        from . import _join, _native
+
+        torch = _native.require_gpu()
+        st = self._resolved_storage()
+        fold.update(segments_folded=0, fold_ms=0.0, empty=False)
+        token_fn = getattr(st, "array_segments_token", None)
+        kept = self._one_join
+        if kept is not None and callable(token_fn) and kept[0] == (id(st), token_fn(), band_bytes, dev.index):
+            fold["empty"] = kept[1] is None
+            return kept[1]
+        if callable(getattr(st, "array_segments_snapshot", None)):
+            segs, token = st.array_segments_snapshot(band_bytes)
+        else:
+            segs, token = (st.array_segments(band_bytes) if callable(getattr(st, "array_segments", None)) else None), None
+        if segs is None:
+            raise RuntimeError("pairs_above joins on the store's bucket arrays: it needs a store that keeps every bucket as "
+                               "arrays (packed_ingest into InMemoryStorage, band keys of at most 6 bytes; no op-tuple buckets)")
+        one, fold_ms, folded = _join.fold_segments(segs)
+        seg = None
+        if one is not None and int(one.members.shape[0]):
+            with torch.cuda.device(dev):
+                seg = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+                            for a in (one.codes, one.offsets, one.members))
+        fold.update(segments_folded=folded, fold_ms=fold_ms, empty=seg is None)
+        self._one_join = None if token is None else ((id(st), token, band_bytes, dev.index), seg, st)
+        return seg
+
+    def recall_pairs_above(self, threshold) -> Dict[str, Any]:
+        """What the LSH self-join finds of the true near-duplicate pairs, measured: the truth is :meth:`pairs_exact_above`
+        ``(threshold)``, what the index finds is :meth:`pairs_above` ``(threshold)`` - a subset of the truth, judged by the same
+        kernel.  Returns ``recall`` (``kept / truth_pairs``; 1.0 when there is no truth), ``precision`` (``kept / emitted``:
+        the share of the candidate pairs that reach the threshold; 1.0 when nothing was emitted), ``truth_pairs``,
+        ``candidates`` (distinct candidate pairs), ``kept`` and ``expected``: the mean over the truth pairs of the collision
+        law :meth:`recall_above` reports (``lshrs_amd._exact.collision_law``; NaN when there is no truth)."""
+        from ._exact import collision_law
+
+        _, _, t_scores = self.pairs_exact_above(threshold, return_arrays=True)
+        ids_a, _, _, _ = self.pairs_above(threshold, return_arrays=True)
+        truth_pairs, kept, emitted = int(t_scores.shape[0]), int(ids_a.shape[0]), int(self.last_search_stats["emitted"])
+        return {"recall": kept / truth_pairs if truth_pairs else 1.0, "precision": kept / emitted if emitted else 1.0,
+                "truth_pairs": truth_pairs, "candidates": emitted, "kept": kept,
+                "expected": collision_law(t_scores, self._config["num_bands"], self._config["rows_per_band"])}
 
     def _query_many_device(self, arr, top_k, top_p, corpus):
         """``query_many`` with everything between the upload of the queries and the download of the answers on the device."""

@@ -386,6 +386,24 @@ class DeviceVectors:
         self.last_search_stats = stats
         return got
 
+    def lsh_pairs_above(self, threshold, codes, offsets, members, num_bands: int, band_bytes: int, *, return_tensors: bool = False,
+                        **kwargs):
+        """The candidate pairs of ONE bucket segment (``codes``, ``offsets``, ``members``: device int64 tensors, the members
+        being ids of this store) at or above a cosine ``threshold``, under the caller's ids: ``(ids_a, ids_b, scores,
+        collisions)`` - :func:`lshrs_amd.lsh_pairs_above` over the row block where it is, the members translated to its rows
+        (``kwargs``: its ``min_collisions``, ``max_bucket``, ``max_pairs``, ``max_raw_pairs``).  A member without a stored
+        vector raises ``IndexError``.  The rows and the table are two snapshots taken one after the other, without a lock across
+        both.  What the call did is left in ``last_search_stats``."""
+        from ._join import lsh_pairs_above
+
+        rows, row_ids = self._search_snapshot()
+        member_rows, _ = self.translate(members)
+        stats: Dict[str, Any] = {}
+        got = lsh_pairs_above(rows, threshold, codes, offsets, member_rows, num_bands, band_bytes, row_ids=row_ids,
+                              return_tensors=return_tensors, stats=stats, **kwargs)
+        self.last_search_stats = stats
+        return got
+
     def neighbors(self, k: int = 10, *, method: str = "auto", return_tensors: bool = False):
         """The ``k`` OTHER stored vectors nearest to every stored vector by cosine, exactly, under the caller's ids - the k-NN
         graph of the store: ``(ids (n,) int64 ascending, neighbors (n, kk) int64, scores (n, kk) float32)``, ``kk = min(k,
