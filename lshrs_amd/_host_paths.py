@@ -56,7 +56,9 @@ class _HostPaths:
         if arr.shape[1] != self.dim:
             raise ValueError(f"Expected vectors of dimension {self.dim}, received {arr.shape[1]}")
         arr = np.ascontiguousarray(arr)
-        if not arr.flags.writeable:  # torch.from_numpy refuses read-only buffers (np.frombuffer views)
+        # torch.from_numpy refuses read-only buffers (np.frombuffer views); ONE row may be "contiguous" under any row stride
+        # (v[None]: 0), which the kernels would be handed as the rows' pitch
+        if not arr.flags.writeable or arr.strides[0] != 4 * self.dim:
             arr = arr.copy()
         n = arr.shape[0]
         mode = self.tie_break if tie_break is None else tie_break

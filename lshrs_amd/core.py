@@ -751,7 +751,11 @@ class LSHRS:
         (``packed_ops.merge_csr``: an id once per bucket) and the folded segment is kept on the device beside the store's
         snapshot token, so that a second call folds nothing; ``last_search_stats["fold_ms"]`` says what this call's fold cost.
         An id that sits in two different buckets of one band - indexed under two signatures and never deleted - raises
-        ``ValueError`` before any pair is emitted; an id in the buckets without a vector raises ``IndexError``.  The vectors and
+        ``ValueError`` before any pair is emitted; an id in the buckets without a vector raises ``IndexError``.  That refusal
+        sees COUNTED buckets only (2 .. ``max_bucket`` members): an id under a second signature whose old buckets hold nobody
+        else - its old partners were deleted - is NOT refused today.  It is joined out of whatever counted buckets it sits in
+        and scored under its latest vector, so every pair returned is still a pair of :meth:`pairs_exact_above` with that
+        score; it is refused as soon as, in some band, its old and its new bucket both count.  The vectors and
         the buckets are two snapshots taken one after the other, without a lock across both: an ``index()`` that lands between
         them can surface as that ``IndexError``.  Without a corpus or a store the call raises what :meth:`pairs_exact_above`
         raises; an empty index gives an empty answer.  ``last_search_stats`` receives ``buckets``, ``skipped_buckets``,

@@ -208,7 +208,8 @@ class DeviceVectors:
                     x = x.contiguous()
                 status = torch.empty(n, dtype=torch.uint8, device=self._dev)
                 entry = _QUANTIZE[self.dtype]
-                _native.check(getattr(lib, entry)(x.data_ptr(), n, int(x.stride(0)), self.dim, tail.data_ptr(), self.dim,
+                pitch = int(x.stride(0)) if n > 1 else self.dim     # (ONE row is contiguous under any row stride: v[None] has 0)
+                _native.check(getattr(lib, entry)(x.data_ptr(), n, pitch, self.dim, tail.data_ptr(), self.dim,
                                                   status.data_ptr(), stream), entry)
                 bad = torch.nonzero(status).reshape(-1)
                 if bad.numel():         # (the rows written stay behind `_used`: the next add overwrites them)

@@ -9,11 +9,11 @@ import functools
 import numpy as np
 import pytest
 
-from tests._join_reference import join_reference
+from tests._join_reference import buckets_reference, join_reference
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = ((1, 1), (3, 1), (16, 2), (33, 1), (128, 1), (8, 6), (16, 4))
+SHAPES = ((1, 1), (3, 1), (16, 2), (33, 1), (128, 1), (8, 6), (16, 4), (2, 1), (6, 2), (10, 1))
 PLANTED = (300, 129, 65, 64, 63, 3, 2, 1)          # bucket lengths of band 0, among many small ones
 
 
@@ -116,7 +116,7 @@ def test_max_bucket_counts_in_no_role():
     assert join_reference([seg], max_bucket=5)[0] == {(0, 1): 1}
 
 
-@pytest.mark.parametrize("nb, bb", ((16, 2), (3, 1)))
+@pytest.mark.parametrize("nb, bb", ((16, 2), (3, 1), (6, 2)))
 def test_min_collisions_against_the_reference(nb, bb):
     seg, n_rows = _segment(nb, bb)
     for need in (2, nb):
@@ -173,15 +173,16 @@ def test_two_signatures_are_refused_and_an_id_twice_in_a_bucket_counts_once():
     assert got == {(3, 5): nb, (3, 6): nb, (5, 6): nb} == join_reference([one, again])[0] and raw == 3 * nb
 
 
-def _planted(n, dim, seed):
-    """n float32 rows: 200 of them with two noisy copies each, cosines between about 0.62 and 0.95."""
+def _planted(n, dim, seed, copies=200):
+    """n float32 rows: `copies` of them with two noisy copies each, cosines between about 0.62 and 0.95."""
     rng = np.random.default_rng(seed)
     x = rng.standard_normal((n, dim)).astype(np.float32)
-    src = rng.choice(n // 2, size=200, replace=False)
+    src = rng.choice(n // 2, size=copies, replace=False)
+    assert n // 2 + 2 * copies <= n
     for k in range(2):
-        sigma = rng.uniform(0.3, 1.25, size=(200, 1)).astype(np.float32)
-        x[n // 2 + 200 * k + np.arange(200)] = x[src] * rng.uniform(0.5, 2.0, size=(200, 1)).astype(np.float32) \
-            + sigma * rng.standard_normal((200, dim)).astype(np.float32)
+        sigma = rng.uniform(0.3, 1.25, size=(copies, 1)).astype(np.float32)
+        x[n // 2 + copies * k + np.arange(copies)] = x[src] * rng.uniform(0.5, 2.0, size=(copies, 1)).astype(np.float32) \
+            + sigma * rng.standard_normal((copies, dim)).astype(np.float32)
     return x
 
 
@@ -272,3 +273,165 @@ def test_what_the_join_refuses_and_the_empty_index():
     tuples.index(ids, x)
     with pytest.raises(RuntimeError, match="array"):
         tuples.pairs_above(0.6)
+
+
+@pytest.mark.parametrize("dtype", ("float32", "bfloat16"))
+def test_row_ids_in_another_order_than_the_rows_and_device_tensors_back(dtype):
+    """lsh_pairs_above(row_ids=...): the emit delivers ROW pairs with the lower row first, the answer is oriented by ID."""
+    import torch
+
+    from lshrs_amd import exact_pairs_above, lsh_pairs_above
+    from lshrs_amd.packed_ops import _csr_host
+
+    n, dim, t, nb = 600, 48, 0.6, 6
+    corpus = torch.from_numpy(_planted(n, dim, 21, copies=100)).cuda().to(getattr(torch, dtype))
+    rng = np.random.default_rng(22)
+    row_ids = (1 << 40) + 1 + 104729 * rng.permutation(n).astype(np.int64)
+    row_ids[rng.choice(n, size=37, replace=False)] = -1            # rows no id points at: members of no bucket
+    live = np.flatnonzero(row_ids >= 0).astype(np.int64)
+    assert live.shape[0] == n - 37 and row_ids[live].min() > 1 << 40
+    seg = _csr_host(live, rng.integers(0, 8, size=(live.shape[0], nb, 1)).astype(np.uint8))
+    rows, ref_stats = join_reference([seg])
+    turned = np.mean([row_ids[a] > row_ids[b] for a, b in rows])
+    assert 0.4 < turned < 0.6, "about half of the row pairs have the higher id at the lower row"
+    cand = {(int(min(row_ids[a], row_ids[b])), int(max(row_ids[a], row_ids[b]))): c for (a, b), c in rows.items()}
+    assert len(cand) == len(rows)
+    ea, eb, es, keep = _filtered(exact_pairs_above(corpus, t, row_ids=row_ids), cand)
+    assert keep.any() and not keep.all(), "the candidates must hit some of the truth and miss some"
+    dev = [torch.from_numpy(a).cuda() for a in (seg.codes, seg.offsets, seg.members)]
+    stats = {}
+    got = lsh_pairs_above(corpus, t, *dev, nb, 1, row_ids=row_ids, stats=stats)
+    assert [a.dtype for a in got] == [np.int64, np.int64, np.float32, np.int32]
+    assert np.array_equal(got[0], ea) and np.array_equal(got[1], eb) and np.all(got[0] < got[1])
+    assert np.array_equal(got[2].view(np.uint32), es.view(np.uint32))
+    assert got[3].tolist() == [cand[p] for p in zip(ea.tolist(), eb.tolist())] and max(got[3]) > 1
+    assert stats["emitted"] == len(cand) and stats["kept"] == len(ea) and stats["raw_pairs"] == ref_stats["raw_pairs"]
+    assert stats["buckets"] == ref_stats["buckets"] and stats["skipped_buckets"] == 0
+    tensors = lsh_pairs_above(corpus, t, *dev, nb, 1, row_ids=row_ids, return_tensors=True)
+    assert len(tensors) == 4 and all(isinstance(x, torch.Tensor) and x.device == corpus.device for x in tensors)
+    assert [x.dtype for x in tensors] == [torch.int64, torch.int64, torch.float32, torch.int32]
+    for x, y in zip(tensors, got):
+        assert np.array_equal(x.cpu().numpy().view(np.uint32), y.view(np.uint32))
+
+
+def _near_copy(v, rng, eps=0.045):
+    """v and a little noise: a cosine of about 1 / sqrt(1 + eps^2) = 0.999 with v."""
+    noise = rng.standard_normal(v.shape).astype(np.float32)
+    return (v + eps * np.linalg.norm(v) / np.linalg.norm(noise) * noise).astype(np.float32)
+
+
+def _store_index(dtype):
+    """1500 planted rows indexed in three calls under scattered ids, the vectors kept by the index: (index, x, ids, rng)."""
+    from lshrs_amd import LSHRS, InMemoryStorage
+
+    n, dim = 1500, 64
+    x = _planted(n, dim, 31)
+    rng = np.random.default_rng(32)
+    ids = (1 << 40) + 7919 * rng.permutation(n).astype(np.int64)
+    index = LSHRS(dim=dim, num_perm=64, num_bands=8, rows_per_band=8, storage=InMemoryStorage(), packed_ingest=True,
+                  keep_vectors=dtype)
+    for lo in range(0, n, 500):
+        index.index(ids[lo:lo + 500], x[lo:lo + 500])
+    return index, x, ids, rng
+
+
+def _most_collisions(got, but=()):
+    """The pair of the answer `got` with the most collisions among those that involve none of `but`."""
+    ok = [k for k in range(len(got[0])) if int(got[0][k]) not in but and int(got[1][k]) not in but]
+    k = max(ok, key=lambda k: (int(got[3][k]), -k))
+    return int(got[0][k]), int(got[1][k])
+
+
+def _a_stranger(index, ids, to, but=()):
+    """The first id that shares no bucket with `to` and is none of `but`."""
+    cand = join_reference(index._storage.array_segments(1))[0]
+    return next(int(i) for i in ids.tolist() if i != to and i not in but and (min(i, to), max(i, to)) not in cand)
+
+
+def _same(one, two):
+    return all(np.array_equal(a.view(np.uint32) if a.dtype == np.float32 else a, b.view(np.uint32) if b.dtype == np.float32 else b)
+               and a.dtype == b.dtype for a, b in zip(one, two))
+
+
+@pytest.mark.parametrize("dtype", ("bfloat16", "int8"))
+def test_the_store_route_after_reindexing_and_compaction(dtype):
+    """DeviceVectors.lsh_pairs_above over a row block with superseded rows (map rows that stay all -1, row_ids of -1, members
+    translated to the LATEST row), after compact(), after delete() and re-index, and the refusal of an id under two signatures
+    through the whole LSHRS call."""
+    index, x, ids, rng = _store_index(dtype)
+    t = 0.6
+    row_of = {int(i): r for r, i in enumerate(ids.tolist())}
+    # 200 ids a second time, the SAME vectors: 200 superseded rows, the same buckets
+    again = rng.choice(ids.shape[0], size=200, replace=False)
+    index.index(ids[again], x[again])
+    assert index.vectors.stats()["dead"] == 200 and index.vectors.stats()["live"] == 1500
+    got, exact, _ = _check_whole_call(index, t)
+    # compact(): other rows, the same answer, and the buckets did not change - nothing is folded again
+    index.vectors.compact()
+    assert index.vectors.stats()["dead"] == 0 and index.vectors.stats()["rows"] == 1500
+    after = index.pairs_above(t, return_arrays=True)
+    assert index.last_search_stats["segments_folded"] == 0
+    assert _same(after, got) and len(got[0]) > 0
+    assert _same(index.pairs_exact_above(t, return_arrays=True), exact)
+    # X, which has a partner above the threshold, deleted and indexed again under a near copy of Z's vector
+    big_x, partner = int(got[0][0]), int(got[1][0])
+    big_z = _a_stranger(index, ids, big_x, but=(partner,))
+    index.delete([big_x])
+    index.index(np.array([big_x], dtype=np.int64), _near_copy(x[row_of[big_z]], rng)[None])
+    assert index.vectors.stats()["dead"] == 1
+    got, exact, _ = _check_whole_call(index, t)
+    pairs = set(zip(got[0].tolist(), got[1].tolist()))
+    assert (min(big_x, big_z), max(big_x, big_z)) in pairs
+    # W indexed under a second vector WITHOUT a delete: old vector near Y's, new vector near Z2's
+    special = (big_x, big_z, partner)
+    big_w, big_y = _most_collisions(got, but=special)
+    big_z2 = _a_stranger(index, ids, big_w, but=special + (big_y,))
+    index.index(np.array([big_w], dtype=np.int64), _near_copy(x[row_of[big_z2]], rng)[None])
+    segments = index._storage.array_segments(1)
+    mine = {}
+    for code, members in buckets_reference(segments).items():
+        if big_w in members and len(members) >= 2:
+            mine.setdefault(code >> 8, []).append(members)
+    assert any(len(b) == 2 and any(big_y in m for m in b) and any(big_z2 in m and big_y not in m for m in b) for b in mine.values()), \
+        "in some band W must share a bucket with Y under the old keys and another with Z2 under the new ones"
+    cand = join_reference(segments)[0]
+    assert (min(big_w, big_y), max(big_w, big_y)) in cand and (min(big_w, big_z2), max(big_w, big_z2)) in cand
+    with pytest.raises(ValueError, match="two signatures"):
+        index.pairs_above(t)
+    with pytest.raises(ValueError, match="two signatures"):
+        index.pairs_above(t, return_arrays=True, min_collisions=2)
+    ea, eb, es = index.pairs_exact_above(t, return_arrays=True)
+    assert (min(big_w, big_z2), max(big_w, big_z2)) in set(zip(ea.tolist(), eb.tolist()))      # (W's vector is the latest)
+    # delete() cures it
+    index.delete([big_w])
+    _check_whole_call(index, t)
+
+
+@pytest.mark.parametrize("dtype", ("bfloat16", "int8"))
+def test_a_second_signature_whose_old_partner_is_gone(dtype):
+    """As W above, but the old partner was deleted first: W's old buckets hold W alone, unless somebody else shares one, and a
+    bucket of one member does not count - the row map does not see it.  Pinned here is what must hold either way: the call
+    refuses the id, or every pair it returns is a pair of pairs_exact_above with that score, bit for bit (W is scored under
+    its latest vector).  LSHRS.pairs_above's docstring says which of the two happens when.  With this corpus (1500 rows over
+    256 keys a band) W's old buckets keep 4 to 13 members, old and new bucket count in every band, and the call raises today."""
+    index, x, ids, rng = _store_index(dtype)
+    t = 0.6
+    row_of = {int(i): r for r, i in enumerate(ids.tolist())}
+    got = index.pairs_above(t, return_arrays=True)
+    big_w, big_y = _most_collisions(got)
+    big_z = _a_stranger(index, ids, big_w, but=(big_y,))
+    index.delete([big_y])
+    index.index(np.array([big_w], dtype=np.int64), _near_copy(x[row_of[big_z]], rng)[None])
+    codes_of_w = [code for code, members in buckets_reference(index._storage.array_segments(1)).items() if big_w in members]
+    assert len(codes_of_w) > 8, "W must sit in two buckets of some band"
+    ea, eb, es = index.pairs_exact_above(t, return_arrays=True)
+    truth = dict(zip(zip(ea.tolist(), eb.tolist()), es.view(np.uint32).tolist()))
+    assert (min(big_w, big_z), max(big_w, big_z)) in truth
+    try:
+        ga, gb, gs, _ = index.pairs_above(t, return_arrays=True)
+    except ValueError as exc:
+        assert "two signatures" in str(exc)
+    else:
+        assert len(ga) > 0
+        for pair, bits in zip(zip(ga.tolist(), gb.tolist()), gs.view(np.uint32).tolist()):
+            assert truth.get(pair) == bits, pair

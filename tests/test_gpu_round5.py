@@ -189,6 +189,25 @@ def test_pipelined_index_leaves_the_buckets_of_the_per_vector_flow(torch_mod, nb
         _ingest.CsrIngest.chunk_rows = old
 
 
+def test_one_vector_indexed_as_a_view_whose_row_stride_is_zero(torch_mod):
+    """`index([i], v[None])` on a storage that takes bucket arrays: NumPy calls the one-row view contiguous under its row stride
+    of 0, which must not reach the kernels as the rows' pitch (LSHRS_E_BADARG).  Same buckets as the same row with a pitch."""
+    from lshrs_amd import LSHRS, InMemoryStorage
+
+    kw = dict(dim=64, num_perm=64, num_bands=8, rows_per_band=8, seed=9, packed_ingest=True)
+    v = np.random.default_rng(3).standard_normal(64).astype(np.float32)
+    assert v[None].strides[0] == 0 and v[None].flags.c_contiguous
+    for keep in (None, "bfloat16", "int8"):          # (the index's own vector store quantizes the same one row)
+        view, pitched = InMemoryStorage(), InMemoryStorage()
+        one = LSHRS(storage=view, keep_vectors=keep, **kw)
+        two = LSHRS(storage=pitched, keep_vectors=keep, **kw)
+        one.index(np.array([5], dtype=np.int64), v[None])
+        two.index(np.array([5], dtype=np.int64), v.reshape(1, -1).copy())
+        assert _store_dict(view) == _store_dict(pitched) and len(_store_dict(view)) == 8
+        if keep is not None:
+            assert len(one.vectors) == 1 and torch_mod.equal(one.vectors.rows.view(torch_mod.uint8), two.vectors.rows.view(torch_mod.uint8))
+
+
 def test_eight_lanes_deal_loader_batches_round_robin_and_store_them_in_order(torch_mod):
     """`LSHRS(devices=[0] * 8)` (SURVEY §8e without the hardware: eight lanes on the one GPU): `create_signatures` deals whole
     loader batches - ragged ones - to the lanes round-robin; the storage receives their bucket arrays in batch order, the same

@@ -1,6 +1,6 @@
 """Host side of the LSH self-join (lshrs_amd.lsh_pairs_above, lshrs_join_*): the exports and where they are declared, the
 workspace's size, the C entries' argument checks, what the Python layers decide before any GPU call, the plain-Python
-reference on a case written by hand, and the shared collision law.  No GPU."""
+reference on a case written by hand (the pairs, the row map, the triangular index), and the shared collision law.  No GPU."""
 
 from __future__ import annotations
 
@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests._join_reference import join_reference
+from tests._join_reference import hand_segment, join_reference, pair_of, rowmap_reference
 
 JOIN_EXPORTS = ("lshrs_join_workspace_bytes", "lshrs_join_rowmap_i64", "lshrs_join_emit_i64")
 
@@ -175,13 +175,7 @@ def test_good_arguments_get_as_far_as_the_gpu(monkeypatch):
 
 
 def test_the_reference_on_a_case_written_by_hand():
-    from lshrs_amd.packed_ops import BucketCSR
-
-    def seg(buckets, bb=1):
-        codes = np.array(sorted(buckets), dtype=np.int64)
-        lens = [len(buckets[c]) for c in codes.tolist()]
-        members = np.array([m for c in codes.tolist() for m in buckets[c]], dtype=np.int64)
-        return BucketCSR(bb, (codes >> 8 * bb).astype(np.int32), None, codes, np.r_[0, np.cumsum(lens)].astype(np.int64), members, 0)
+    seg = hand_segment
 
     # band 0: {1, 2, 3} under key 7, {4} under key 9; band 1: {2, 3} under key 1 (3 through the second segment), {1, 4, 5, 6}
     # under key 2
@@ -196,6 +190,43 @@ def test_the_reference_on_a_case_written_by_hand():
     pairs, stats = join_reference([one, two], max_bucket=2)
     assert pairs == {(2, 3): 1} and stats["skipped_buckets"] == 2           # (the oversized bucket is no collision either)
     assert join_reference([], 1) == ({}, {"buckets": 0, "skipped_buckets": 0, "raw_pairs": 0})
+
+
+def test_the_row_map_reference_on_the_case_written_by_hand():
+    # the buckets of the case above as ONE segment (what a fold makes of them), sorted by code: g = 0 .. 3
+    seg = hand_segment({0x007: [1, 2, 3], 0x009: [4], 0x101: [2, 3], 0x102: [1, 4, 5, 6]})
+    none = [-1, -1]
+    assert rowmap_reference(seg, 8, 2, 1).tolist() == [none, [0, 3], [0, 2], [0, 2], [-1, 3], [-1, 3], [-1, 3], none]
+    got = rowmap_reference(seg, 8, 2, 1)
+    assert got.dtype == np.int32 and got.shape == (8, 2)
+    # buckets of more than max_bucket entries count in no role; a bucket of one entry never does
+    assert rowmap_reference(seg, 8, 2, 1, max_bucket=3).tolist() == [none, [0, -1], [0, 2], [0, 2], none, none, none, none]
+    assert rowmap_reference(seg, 8, 2, 1, max_bucket=2).tolist() == [none, none, [-1, 2], [-1, 2], none, none, none, none]
+    # what a valid segment never holds defines no cell: rows outside [0, n_rows), bands outside [0, num_bands)
+    assert rowmap_reference(seg, 4, 1, 1).tolist() == [[-1], [0], [0], [0]]
+    odd = hand_segment({0x007: [1, -1, 3], 0x008: [3, 2]})
+    assert rowmap_reference(odd, 4, 1, 1).tolist() == [[-1], [0], [1], [0]]          # (two buckets of one band: the first)
+
+
+def _inverts(t):
+    i, j = pair_of(t)
+    return type(i) is int and type(j) is int and 0 <= i < j and j * (j - 1) // 2 + i == t
+
+
+def test_pair_of_inverts_the_triangular_index():
+    assert [pair_of(t) for t in range(7)] == [(0, 1), (0, 2), (1, 2), (0, 3), (1, 3), (2, 3), (0, 4)]
+    assert all(_inverts(t) for t in range(5000))
+    assert sorted(pair_of(t) for t in range(4950)) == [(i, j) for i in range(100) for j in range(i + 1, 100)]
+    for centre in (1 << 24, 1 << 31, 1 << 32, 1 << 52):
+        assert all(_inverts(t) for t in range(centre - 3, centre + 4)), centre
+    for j in (2, 3, 4097, 65536, 92682, 92683, (1 << 26) + 1):
+        first = j * (j - 1) // 2
+        assert all(_inverts(t) for t in range(max(0, first - 3), first + 4)), j
+        assert pair_of(first) == (0, j) and pair_of(first - 1) == (j - 2, j - 1) and pair_of(first + j - 1) == (j - 1, j)
+    # (where a float32 and a 32-bit t stop being exact: what the GPU test's windows are placed around)
+    assert pair_of(1 << 24)[1] == 5793 and pair_of(1 << 32)[1] == 92682
+    with pytest.raises(ValueError):
+        pair_of(-1)
 
 
 def test_folding_segments_is_merge_csr_and_is_timed():
