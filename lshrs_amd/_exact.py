@@ -28,6 +28,12 @@ its buckets' pairs with, too).
 nearest to it - the stored rows are their own queries, a block at a time, no row enters its own window, and the settle rule and
 the gather fallback are those of ``exact_top_k``.
 
+Each layer is one text.  The two selections share ``_check_selection`` and ``_method_plan`` (arguments; scan or gather, window,
+epsilon), ``_scan_selecting`` (the windows' buffers and the launch behind ``scan_windows`` and ``scan_knn``), ``_window_answer``
+(from the windows to ids, scores and the settled queries: the tie rule and the settle rule live there and nowhere else),
+``_live_by_id`` and ``_gather``.  The two emitting passes share ``_scan_emitting`` and ``_all_pairs``; the two joins
+``_judge_pairs``; all of them ``_rows_args``, ``_scan_workspace`` and ``_finish``.
+
 No CPU compute path: the host moves arrays, decides which queries are settled from three numbers per query, and keeps counts.
 """
 
@@ -106,9 +112,23 @@ def settled(count, window: int, a_window, s_k, epsilon: float) -> np.ndarray:
         return (count < int(window)) | (a + float(epsilon) <= s)
 
 
-def _check_method(method: str) -> None:
+def _check_selection(k, method) -> int:
+    """``k`` as an int; ``ValueError`` for a ``method`` or a ``k`` that ``exact_top_k`` and ``exact_knn`` do not take.  Pure
+    host: it runs before anything touches the GPU."""
     if method not in METHODS:
         raise ValueError("method must be 'auto', 'scan' or 'gather'")
+    if int(k) <= 0:
+        raise ValueError("k must be > 0")
+    return int(k)
+
+
+def _method_plan(k: int, method: str, dtype, dim: int):
+    """How a selection of ``k`` (checked: :func:`_check_selection`) goes over rows of ``dtype`` and ``dim`` elements:
+    ``(use_scan, window, eps)`` - whether the first pass runs, the window it keeps per query (0 without it: what ``stats``
+    report as ``window``) and ``scan_epsilon``."""
+    max_window = scan_max_window()
+    use_scan = method == "scan" or (method == "auto" and 2 * k <= max_window)
+    return use_scan, choose_window(k, max_window) if use_scan else 0, scan_epsilon(dtype, dim)
 
 
 def _scan_workspace(torch, lib, sizer: str, dev, *shape):
@@ -118,6 +138,30 @@ def _scan_workspace(torch, lib, sizer: str, dev, *shape):
     if nbytes < 0:
         _native.check(nbytes, sizer)
     return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _scan_selecting(corpus, family: str, sizer: str, q: int, window: int, empty: bool, sizer_shape, head, row_ids):
+    """The plumbing of the two selecting entries (``family``: "topk" or "knn"): the windows of ``q`` queries - rows,
+    approximate scores, counts - and the error bits; unless ``empty``, the workspace (``sizer`` of ``sizer_shape``) and the
+    launch, ``head`` being the entry's own arguments between ``row_ids`` and ``out_rows``.  Returns ``(rows, approx, count,
+    err)``."""
+    torch = _native.require_gpu()
+    lib = _native.load()
+    entry = f"lshrs_scan_{family}_" + corpus_suffix(corpus)
+    dev = corpus.device
+    rows = torch.empty((max(q, 0), window), dtype=torch.int64, device=dev)
+    approx = torch.empty((max(q, 0), window), dtype=torch.float32, device=dev)
+    count = torch.empty((max(q, 0),), dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    if empty:
+        return rows, approx, count, err
+    with torch.cuda.device(dev):
+        ws = _scan_workspace(torch, lib, sizer, dev, *sizer_shape)
+        _native.check(getattr(lib, entry)(corpus.data_ptr(), int(corpus.shape[0]), int(corpus.stride(0)), int(corpus.shape[1]),
+                                          row_ids.data_ptr() if row_ids is not None else None, *head,
+                                          rows.data_ptr(), approx.data_ptr(), count.data_ptr(), ws.data_ptr(), err.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream), entry)
+    return rows, approx, count, err
 
 
 def _scan_emitting(corpus, family: str, first_dtype, capacity: int, empty: bool, sizer_shape, head, row_ids):
@@ -180,24 +224,9 @@ def scan_windows(corpus, queries, window: int, row_ids=None):
     """Device-level entry of the first pass: ``corpus`` (m, dim) as ``corpus_suffix`` accepts it, ``queries`` (q, dim) float32
     contiguous on the same device, ``row_ids`` optional int64 (m,) there.  Returns ``(rows (q, window) int64, approx (q, window)
     float32, count (q,) int32, err int32[1])`` as ``lshrs_scan_topk_*`` leaves them."""
-    torch = _native.require_gpu()
-    lib = _native.load()
-    entry = "lshrs_scan_topk_" + corpus_suffix(corpus)
-    dev = corpus.device
     q, m, dim = int(queries.shape[0]), int(corpus.shape[0]), int(corpus.shape[1])
-    rows = torch.empty((q, window), dtype=torch.int64, device=dev)
-    approx = torch.empty((q, window), dtype=torch.float32, device=dev)
-    count = torch.empty((q,), dtype=torch.int32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    if q == 0:
-        return rows, approx, count, err
-    with torch.cuda.device(dev):
-        ws = _scan_workspace(torch, lib, "lshrs_scan_workspace_bytes", dev, q, m, dim, window)
-        _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim,
-                                          row_ids.data_ptr() if row_ids is not None else None, queries.data_ptr(), q, window,
-                                          rows.data_ptr(), approx.data_ptr(), count.data_ptr(), ws.data_ptr(), err.data_ptr(),
-                                          torch.cuda.current_stream(dev).cuda_stream), entry)
-    return rows, approx, count, err
+    return _scan_selecting(corpus, "topk", "lshrs_scan_workspace_bytes", q, window, q == 0, (q, m, dim, window),
+                           (queries.data_ptr(), q, window), row_ids)
 
 
 def _rescore(torch, corpus, queries, rows, count):
@@ -206,8 +235,42 @@ def _rescore(torch, corpus, queries, rows, count):
     dev = corpus.device
     q, w = int(rows.shape[0]), int(rows.shape[1])
     scores = torch.full((q, w), float("-inf"), dtype=torch.float32, device=dev)
-    off = torch.arange(q, dtype=torch.int64, device=dev) * w
+    off = torch.arange(0, q * w, w, dtype=torch.int64, device=dev)
     return cosine_ragged_device(corpus, queries, rows, off, count, q * w, scores=scores)
+
+
+def _window_answer(torch, corpus, queries, d_ids, rows, approx, count, err, kk: int, window: int, margin: float):
+    """From the first pass's windows to the answer they hold: ``rows`` / ``approx`` / ``count`` / ``err`` as
+    :func:`scan_windows` or :func:`scan_knn` leave them for the float32 ``queries`` (u, dim).  Returns ``(ids (u, kw), scores
+    (u, kw), done)`` with ``kw = min(kk, window)``: the window's best by the rerank's score, equal scores by ascending id, and
+    which queries that settles (:func:`settled` with ``margin``: epsilon plus :func:`rerank_rounding`).  Five things cross to
+    the host: the error words of the pass and of the rescoring - a zero vector raises here - and per query ``count``, the
+    window's last approximate score and the k-th rescored one."""
+    # the window in ascending order of id (padding last): the tie rule of the top-k kernel then is ascending id
+    wid = rows if d_ids is None else torch.where(rows >= 0, d_ids[rows.clamp(min=0)], rows)
+    key = torch.where(rows >= 0, wid, torch.iinfo(torch.int64).max)
+    by_id = torch.argsort(key, dim=1)
+    rows_s, wid = torch.gather(rows, 1, by_id).contiguous(), torch.gather(wid, 1, by_id)
+    exact, err2 = _rescore(torch, corpus, queries, rows_s, count)
+    if int(err.item()) & 5 or int(err2.item()) & 5:
+        raise ValueError("Cannot normalize zero vector")
+    kw = min(kk, window)
+    order, best = topk_desc_device(exact, kw)
+    s_k = best[:, kw - 1] if kw == kk else torch.full((int(rows.shape[0]),), float("-inf"), device=corpus.device)
+    done = settled(count.cpu().numpy(), window, approx[:, window - 1].cpu().numpy(), s_k.cpu().numpy(), margin)
+    return torch.gather(wid, 1, order.long()), best, done
+
+
+def _live_by_id(torch, d_ids, m: int, dev):
+    """``(live_rows, live_ids)``, both contiguous: the rows of ``row_ids`` ``d_ids`` (None: all ``m``, under their index) that
+    exist, in ascending order of their ids, and those ids."""
+    if d_ids is None:
+        live_rows = torch.arange(m, dtype=torch.int64, device=dev)
+        return live_rows, live_rows
+    live_rows = torch.nonzero(d_ids >= 0).reshape(-1)
+    live_ids = d_ids[live_rows]
+    by_id = torch.argsort(live_ids)
+    return live_rows[by_id].contiguous(), live_ids[by_id].contiguous()
 
 
 def _gather(torch, corpus, queries, live_rows, live_ids, kk: int):
@@ -292,52 +355,27 @@ def exact_top_k(queries, corpus, k: int, *, row_ids=None, method: str = "auto", 
     ``stats``: a dict that receives ``queries``, ``settled_first_pass``, ``gathered``, ``window`` and ``epsilon``.
 
     A query or a live row of zero norm raises ``ValueError("Cannot normalize zero vector")``, as the rerank does."""
-    _check_method(method)
-    if int(k) <= 0:
-        raise ValueError("k must be > 0")
-    k = int(k)
+    k = _check_selection(k, method)
     torch = _native.require_gpu()
     d_q, d_ids, q, m, dim = _search_args(queries, corpus, row_ids, "exact_top_k")
     dev = corpus.device
     with torch.cuda.device(dev):
         live = m if d_ids is None else int((d_ids >= 0).sum())
         kk = min(k, live)
-        max_window = scan_max_window()
-        use_scan = method == "scan" or (method == "auto" and 2 * k <= max_window)
-        window = choose_window(k, max_window)
-        eps = scan_epsilon(corpus.dtype, dim)
-        out = {"queries": q, "settled_first_pass": 0, "gathered": 0, "window": window if use_scan else 0, "epsilon": eps}
+        use_scan, window, eps = _method_plan(k, method, corpus.dtype, dim)
+        out = {"queries": q, "settled_first_pass": 0, "gathered": 0, "window": window, "epsilon": eps}
         ids = torch.empty((q, kk), dtype=torch.int64, device=dev)
         scores = torch.empty((q, kk), dtype=torch.float32, device=dev)
         todo = None                                     # queries left to the gather: None = all of them
         if q and kk and use_scan:
-            rows, approx, count, err = scan_windows(corpus, d_q, window, d_ids)
-            # the window in ascending order of id (padding last): the tie rule of the top-k kernel then is ascending id
-            wid = rows if d_ids is None else torch.where(rows >= 0, d_ids[rows.clamp(min=0)], rows)
-            key = torch.where(rows >= 0, wid, torch.full_like(wid, torch.iinfo(torch.int64).max))
-            by_id = torch.argsort(key, dim=1)
-            rows_s, wid = torch.gather(rows, 1, by_id).contiguous(), torch.gather(wid, 1, by_id)
-            exact, err2 = _rescore(torch, corpus, d_q, rows_s, count)
-            if int(err.item()) & 5 or int(err2.item()) & 5:
-                raise ValueError("Cannot normalize zero vector")
-            kw = min(kk, window)
-            order, best = topk_desc_device(exact, kw)
-            s_k = best[:, kw - 1] if kw == kk else torch.full((q,), float("-inf"), device=dev)
-            done = settled(count.cpu().numpy(), window, approx[:, window - 1].cpu().numpy(), s_k.cpu().numpy(),
-                           eps + rerank_rounding(dim))
-            ids[:, :kw] = torch.gather(wid, 1, order.long())
-            scores[:, :kw] = best
+            w_ids, w_scores, done = _window_answer(torch, corpus, d_q, d_ids, *scan_windows(corpus, d_q, window, d_ids), kk,
+                                                   window, eps + rerank_rounding(dim))
+            kw = int(w_ids.shape[1])
+            ids[:, :kw], scores[:, :kw] = w_ids, w_scores
             out["settled_first_pass"] = int(done.sum())
             todo = torch.from_numpy(np.flatnonzero(~done)).to(dev)
         if q and kk and (todo is None or int(todo.numel())):
-            if d_ids is None:
-                live_rows = torch.arange(m, dtype=torch.int64, device=dev)
-                live_ids = live_rows
-            else:
-                live_rows = torch.nonzero(d_ids >= 0).reshape(-1)
-                live_ids = d_ids[live_rows]
-                by_id = torch.argsort(live_ids)
-                live_rows, live_ids = live_rows[by_id].contiguous(), live_ids[by_id].contiguous()
+            live_rows, live_ids = _live_by_id(torch, d_ids, m, dev)
             sub = d_q if todo is None else d_q[todo].contiguous()
             g_ids, g_scores = _gather(torch, corpus, sub, live_rows, live_ids, kk)
             if todo is None:
@@ -615,23 +653,11 @@ def scan_knn(corpus, q_begin: int, q_count: int, window: int, row_ids=None, qblo
     taken as queries per launch (0: the library's plan; else a multiple of 64).  Returns ``(rows (q_count, window) int64, approx
     (q_count, window) float32, count (q_count,) int32, err int32[1])`` as :func:`scan_windows` does: per query row the
     ``window`` other live rows of the largest approximate score; count 0 for a dead query row."""
-    torch = _native.require_gpu()
-    lib = _native.load()
-    entry = "lshrs_scan_knn_" + corpus_suffix(corpus)
-    dev = corpus.device
     q_begin, q, window, qblock = int(q_begin), int(q_count), int(window), int(qblock)
     m, dim = int(corpus.shape[0]), int(corpus.shape[1])
-    rows = torch.empty((max(q, 0), window), dtype=torch.int64, device=dev)
-    approx = torch.empty((max(q, 0), window), dtype=torch.float32, device=dev)
-    count = torch.empty((max(q, 0),), dtype=torch.int32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        ws = _scan_workspace(torch, lib, "lshrs_scan_knn_workspace_bytes", dev, q, m, dim, window, qblock)
-        _native.check(getattr(lib, entry)(corpus.data_ptr(), m, int(corpus.stride(0)), dim,
-                                          row_ids.data_ptr() if row_ids is not None else None, q_begin, q, window, qblock,
-                                          rows.data_ptr(), approx.data_ptr(), count.data_ptr(), ws.data_ptr(), err.data_ptr(),
-                                          torch.cuda.current_stream(dev).cuda_stream), entry)
-    return rows, approx, count, err
+    # (never empty: the entry's argument checks answer for no query rows, too)
+    return _scan_selecting(corpus, "knn", "lshrs_scan_knn_workspace_bytes", q, window, False, (q, m, dim, window, qblock),
+                           (q_begin, q, window, qblock), row_ids)
 
 
 def _knn_chunk(block: int, dim: int, window: int) -> int:
@@ -674,10 +700,7 @@ def exact_knn(corpus, k: int, *, row_ids=None, method: str = "auto", return_tens
     ``k <= 0`` or a bad ``method`` raises ``ValueError`` before anything touches the GPU; a live row of zero norm raises
     ``ValueError("Cannot normalize zero vector")``; rows beyond the kernels raise the ``NativeLibraryError``
     :func:`exact_top_k` raises."""
-    _check_method(method)
-    if int(k) <= 0:
-        raise ValueError("k must be > 0")
-    k = int(k)
+    k = _check_selection(k, method)
     torch = _native.require_gpu()
     lib = _native.load()
     corpus_suffix(corpus)
@@ -685,23 +708,12 @@ def exact_knn(corpus, k: int, *, row_ids=None, method: str = "auto", return_tens
     with torch.cuda.device(dev):
         d_ids = _rows_args(torch, corpus, row_ids, "exact_knn")
         m, dim = int(corpus.shape[0]), int(corpus.shape[1])
-        # the live rows in ascending order of their ids: the order of the answer, and the gather's tie rule
-        if d_ids is None:
-            live_rows = torch.arange(m, dtype=torch.int64, device=dev)
-            live_ids = live_rows
-        else:
-            live_rows = torch.nonzero(d_ids >= 0).reshape(-1)
-            live_ids = d_ids[live_rows]
-            by_id = torch.argsort(live_ids)
-            live_rows, live_ids = live_rows[by_id].contiguous(), live_ids[by_id].contiguous()
+        # in ascending order of their ids: the order of the answer, and the gather's tie rule
+        live_rows, live_ids = _live_by_id(torch, d_ids, m, dev)
         n = int(live_rows.shape[0])
         kk = max(0, min(k, n - 1))
-        max_window = scan_max_window()
-        use_scan = method == "scan" or (method == "auto" and 2 * k <= max_window)
-        window = choose_window(k, max_window)
-        eps = scan_epsilon(corpus.dtype, dim)
-        out = {"rows": m, "live": n, "settled_first_pass": 0, "gathered": 0, "window": window if use_scan else 0,
-               "epsilon": eps, "chunks": 0}
+        use_scan, window, eps = _method_plan(k, method, corpus.dtype, dim)
+        out = {"rows": m, "live": n, "settled_first_pass": 0, "gathered": 0, "window": window, "epsilon": eps, "chunks": 0}
         neighbors = torch.empty((n, kk), dtype=torch.int64, device=dev)
         scores = torch.empty((n, kk), dtype=torch.float32, device=dev)
         if kk:
@@ -721,23 +733,10 @@ def exact_knn(corpus, k: int, *, row_ids=None, method: str = "auto", return_tens
                 todo = None                                 # rows of `mine` left to the gather: None = all of them
                 if use_scan:
                     rows, approx, count, err = scan_knn(corpus, lo, hi - lo, window, d_ids)
-                    rows, approx, count = rows[mine], approx[mine], count[mine].contiguous()
-                    # the window in ascending order of id (padding last): the tie rule of the top-k kernel then is ascending id
-                    wid = rows if d_ids is None else torch.where(rows >= 0, d_ids[rows.clamp(min=0)], rows)
-                    key = torch.where(rows >= 0, wid, torch.full_like(wid, torch.iinfo(torch.int64).max))
-                    by_id = torch.argsort(key, dim=1)
-                    rows_s, wid = torch.gather(rows, 1, by_id).contiguous(), torch.gather(wid, 1, by_id)
-                    exact, err2 = _rescore(torch, corpus, queries, rows_s, count)
-                    if int(err.item()) & 5 or int(err2.item()) & 5:
-                        raise ValueError("Cannot normalize zero vector")
-                    kw = min(kk, window)
-                    order, best = topk_desc_device(exact, kw)
-                    s_k = best[:, kw - 1] if kw == kk else torch.full((int(mine.numel()),), float("-inf"), device=dev)
-                    done = settled(count.cpu().numpy(), window, approx[:, window - 1].cpu().numpy(), s_k.cpu().numpy(),
-                                   eps + rerank_rounding(dim))
-                    at = slot[pos]
-                    neighbors[at, :kw] = torch.gather(wid, 1, order.long())
-                    scores[at, :kw] = best
+                    w_ids, w_scores, done = _window_answer(torch, corpus, queries, d_ids, rows[mine], approx[mine],
+                                                           count[mine].contiguous(), err, kk, window, eps + rerank_rounding(dim))
+                    at, kw = slot[pos], int(w_ids.shape[1])
+                    neighbors[at, :kw], scores[at, :kw] = w_ids, w_scores
                     out["settled_first_pass"] += int(done.sum())
                     todo = torch.from_numpy(np.flatnonzero(~done)).to(dev)
                 if todo is None or int(todo.numel()):

@@ -41,7 +41,7 @@ from .similarity import corpus_entry
 from .similarity import rerank_padded_arrays as _rerank_padded
 from .similarity import top_k_cosine
 from .storage import BucketOperation, default_storage
-from .vectors import NO_VECTOR_MSG, DeviceVectors
+from .vectors import NO_VECTOR_MSG, DeviceVectors, TensorRows
 
 logger = logging.getLogger(__name__)
 
@@ -565,12 +565,7 @@ class LSHRS:
         ``engine``: "auto" (the device path wherever the hasher is the HIP one; a batch with a candidate list beyond the
         kernels' 16 384 entries is counted on the host), "device" (raise instead), "host" (NumPy counting between the two
         launches: round 5's path)."""
-        resident = _device_tensor(vectors)         # queries that already live on a GPU stay there (no copy over the link, no host array)
-        arr = resident if resident is not None else np.asarray(vectors, dtype=np.float32)
-        if len(arr.shape) != 2 or int(arr.shape[1]) != self._dim:
-            raise ValueError(f"Vectors must have shape (n, {self._dim}); received {tuple(arr.shape)}")
-        if resident is not None:
-            arr = resident.float()                  # (itself where it is float32 already)
+        arr = self._query_rows(vectors)
         qh.check_cut(top_k, top_p)
         if engine not in ("auto", "device", "host"):
             raise ValueError("engine must be 'auto', 'device' or 'host'")
@@ -595,7 +590,7 @@ class LSHRS:
                 if engine == "device":
                     raise
         if got is None:
-            got = self._query_many_host(arr if resident is None else arr.cpu().numpy(), top_k, top_p, corpus)
+            got = self._query_many_host(arr if isinstance(arr, np.ndarray) else arr.cpu().numpy(), top_k, top_p, corpus)
         ids, scores, bounds = got
         if return_arrays:
             return ids, scores, bounds
@@ -605,36 +600,30 @@ class LSHRS:
                 return qh.split_rows(ids.tolist(), keep)
             return qh.split_rows(list(zip(ids.tolist(), scores.astype(np.float64).tolist())), keep)
 
-    def _search_queries(self, vectors):
-        """The queries of an exact search as what it searches with: a float32 device tensor where ``vectors`` lives on a
-        GPU, else a float32 host array; ``(n, dim)`` or the ``ValueError`` every query raises."""
+    def _query_rows(self, vectors):
+        """The queries of a batched query or an exact search as what it works with: a float32 device tensor where
+        ``vectors`` lives on a GPU (it stays there: no copy over the link, no host array; itself where it is float32 already),
+        else a float32 host array; ``(n, dim)`` or the ``ValueError`` every query raises."""
         resident = _device_tensor(vectors)
         arr = resident if resident is not None else np.asarray(vectors, dtype=np.float32)
         if len(arr.shape) != 2 or int(arr.shape[1]) != self._dim:
             raise ValueError(f"Vectors must have shape (n, {self._dim}); received {tuple(arr.shape)}")
         return arr if resident is None else resident.float()
 
-    def _search_corpus(self, caller: str, in_store, in_tensor, arr, what):
-        """One exact search of ``arr`` for ``what`` (a ``top_k`` / a threshold): ``in_store`` (``DeviceVectors.search`` /
-        ``search_above``) where the index reranks from a ``DeviceVectors``, else ``in_tensor`` (``exact_top_k`` /
-        ``exact_above``) over the attached corpus on its device.  Sets ``last_search_stats``; without a corpus or a store,
-        raises in the name of ``caller``."""
+    def _searched(self, caller: str):
+        """What the exact searches and the joins go over, as ``vectors.RowSearches``: the ``DeviceVectors`` the index reranks
+        from, else the attached corpus on its device (a host array is uploaded) under its rows' numbers.  Without a corpus
+        or a store, raises in the name of ``caller``.  The caller copies its ``last_search_stats``."""
         corpus = self._rerank_corpus()
         if corpus is None:
             self._require_vector_fetch_fn()
             raise RuntimeError(f"{caller} needs the indexed vectors on the device: set_corpus(...) or keep_vectors=...")
         if isinstance(corpus, DeviceVectors):
-            got = in_store(corpus, arr, what)
-            self.last_search_stats = dict(corpus.last_search_stats)
-            return got
+            return corpus
         from . import _query_device as qd
 
-        stats: Dict[str, Any] = {}
-        table = qd.corpus_on(corpus, getattr(corpus, "device", None) if _device_tensor(corpus) is not None
-                             else self._hasher._torch_device(), self._dim)
-        got = in_tensor(arr, table, what, stats=stats)
-        self.last_search_stats = stats
-        return got
+        return TensorRows(qd.corpus_on(corpus, getattr(corpus, "device", None) if _device_tensor(corpus) is not None
+                                       else self._hasher._torch_device(), self._dim))
 
     def search_exact(self, vectors, top_k: int = 10, *, return_arrays: bool = False):
         """The ``top_k`` indexed vectors nearest to every query by cosine, EXACTLY: every vector of the attached corpus
@@ -646,13 +635,13 @@ class LSHRS:
         there)``.  Without a corpus or a store it raises what a rerank without a fetch function raises.  ``last_search_stats``
         tells what the call did.  A corpus that :meth:`set_corpus` was given as a HOST array is uploaded by every call, as every
         reranked query uploads it (and twice by :meth:`recall`, once for each of its halves): attach a device tensor."""
-        from ._exact import exact_top_k
-
-        arr = self._search_queries(vectors)
+        arr = self._query_rows(vectors)
         qh.check_cut(top_k, None)
         if top_k is None:
             raise ValueError("search_exact needs a top_k")
-        ids, scores = self._search_corpus("search_exact", DeviceVectors.search, exact_top_k, arr, top_k)
+        over = self._searched("search_exact")
+        ids, scores = over.search(arr, top_k)
+        self.last_search_stats = dict(over.last_search_stats)
         if return_arrays:
             return ids, scores
         with _gc_paused():
@@ -679,10 +668,10 @@ class LSHRS:
         errors where there is none.  Returns per query ``[(id, score), ...]``, scores descending and equal scores by ascending
         id - or ``(ids, scores, bounds)`` as :meth:`query_many` returns them with ``return_arrays``.  ``last_search_stats``
         tells what the call did."""
-        from ._exact import exact_above
-
-        arr = self._search_queries(vectors)
-        ids, scores, bounds = self._search_corpus("search_exact_above", DeviceVectors.search_above, exact_above, arr, threshold)
+        arr = self._query_rows(vectors)
+        over = self._searched("search_exact_above")
+        ids, scores, bounds = over.search_above(arr, threshold)
+        self.last_search_stats = dict(over.last_search_stats)
         if return_arrays:
             return ids, scores, bounds
         with _gc_paused():
@@ -694,11 +683,9 @@ class LSHRS:
         (``lshrs_amd.exact_pairs_above``) and with the same errors where there is none.  Returns ``[(id_a, id_b, score),
         ...]`` with ``id_a < id_b``, scores descending and equal scores by ascending ``(id_a, id_b)`` - or ``(ids_a, ids_b,
         scores)`` arrays with ``return_arrays``.  ``last_search_stats`` tells what the call did."""
-        from ._exact import exact_pairs_above
-
-        ids_a, ids_b, scores = self._search_corpus("pairs_exact_above", lambda store, _, t: store.pairs_above(t),
-                                                   lambda _, table, t, stats: exact_pairs_above(table, t, stats=stats), None,
-                                                   threshold)
+        over = self._searched("pairs_exact_above")
+        ids_a, ids_b, scores = over.pairs_above(threshold)
+        self.last_search_stats = dict(over.last_search_stats)
         if return_arrays:
             return ids_a, ids_b, scores
         with _gc_paused():
@@ -710,10 +697,9 @@ class LSHRS:
         errors where there is none.  Returns ``[(id, [(neighbour, score), ...]), ...]`` in ascending order of id, scores
         descending and equal scores by ascending id - or ``(ids (n,), neighbors (n, kk), scores (n, kk))`` arrays with
         ``return_arrays``.  ``last_search_stats`` tells what the call did."""
-        from ._exact import exact_knn
-
-        ids, nbrs, scores = self._search_corpus("neighbors_exact", lambda store, _, k: store.neighbors(k),
-                                                lambda _, table, k, stats: exact_knn(table, k, stats=stats), None, top_k)
+        over = self._searched("neighbors_exact")
+        ids, nbrs, scores = over.neighbors(top_k)
+        self.last_search_stats = dict(over.last_search_stats)
         if return_arrays:
             return ids, nbrs, scores
         with _gc_paused():
@@ -767,19 +753,15 @@ class LSHRS:
         _join.check_join_args(threshold, min_collisions, max_bucket, max_pairs, nb)
         kw = {"min_collisions": int(min_collisions), "max_bucket": max_bucket, "max_pairs": int(max_pairs)}
         fold: Dict[str, Any] = {}
-        empty = (np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.float32), np.empty(0, np.int32))
-
-        def in_store(store, _, t):
-            seg = self._join_segment(store.snapshot()[0].device, bb, fold)
-            return empty if seg is None else store.lsh_pairs_above(t, *seg, nb, bb, **kw)
-
-        def in_tensor(_, table, t, stats):
-            seg = self._join_segment(table.device, bb, fold)        # (the id is the row)
-            return empty if seg is None else _join.lsh_pairs_above(table, t, *seg, nb, bb, stats=stats, **kw)
-
-        ids_a, ids_b, scores, collisions = self._search_corpus("pairs_above", in_store, in_tensor, None, threshold)
-        if fold.pop("empty"):
+        over = self._searched("pairs_above")
+        seg = self._join_segment(over._search_snapshot()[0].device, bb, fold)
+        if fold.pop("empty"):                       # (no segment: an empty index)
+            ids_a, ids_b, scores, collisions = (np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.float32),
+                                                np.empty(0, np.int32))
             self.last_search_stats = {"buckets": 0, "skipped_buckets": 0, "raw_pairs": 0, "emitted": 0, "kept": 0, "launches": 0}
+        else:
+            ids_a, ids_b, scores, collisions = over.lsh_pairs_above(threshold, *seg, nb, bb, **kw)
+            self.last_search_stats = dict(over.last_search_stats)
         self.last_search_stats.update(fold)
         if return_arrays:
             return ids_a, ids_b, scores, collisions

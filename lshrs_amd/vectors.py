@@ -53,7 +53,95 @@ def check_ids(ids) -> np.ndarray:
     return arr
 
 
-class DeviceVectors:
+class RowSearches:
+    """The five searches over device-resident rows under ids - the route from whatever holds such rows to ``_exact`` /
+    ``_join``.  The holder supplies ``dim``, ``_search_snapshot() -> (rows, row_ids)`` (``row_ids``: the id of every row,
+    negative where it has none; None where the id is the row) and ``translate(ids) -> (rows of those ids, ...)``; it
+    receives ``last_search_stats``: what the last search that returned did."""
+
+    def _over_rows(self, fn, *queries, members=None, **kwargs):
+        """``fn(*queries, rows, row_ids=..., stats=..., **kwargs)`` over ONE snapshot of the rows and their ids; ``queries``:
+        those of the two routes that have them, ``(n, dim)``.  ``members`` (the LSH join's: ids of this holder) go in as
+        ``member_rows``, translated after the snapshot.  The stats are stored once ``fn`` has returned: a call that raises
+        leaves the previous ones."""
+        for q in queries:
+            shape = tuple(int(v) for v in getattr(q, "shape", ())) or tuple(np.asarray(q).shape)
+            if len(shape) != 2 or shape[1] != self.dim:
+                raise ValueError(f"Vectors must have shape (n, {self.dim}); received {shape}")
+        rows, row_ids = self._search_snapshot()
+        if members is not None:
+            kwargs["member_rows"] = self.translate(members)[0]
+        stats: Dict[str, Any] = {}
+        got = fn(*queries, rows, row_ids=row_ids, stats=stats, **kwargs)
+        self.last_search_stats = stats
+        return got
+
+    def search(self, queries, k: int = 10, *, method: str = "auto", return_tensors: bool = False):
+        """The ``k`` stored vectors nearest to every query by cosine, exactly, under the caller's ids: ``(ids (q, kk) int64,
+        scores (q, kk) float32)``, ``kk = min(k, len(self))`` - :func:`lshrs_amd.exact_top_k` over the row block where it is,
+        superseded and erased rows left out.  What the call did (queries settled by the first pass, queries gathered, window,
+        epsilon) is left in ``last_search_stats``."""
+        from ._exact import exact_top_k
+
+        return self._over_rows(exact_top_k, queries, k=k, method=method, return_tensors=return_tensors)
+
+    def search_above(self, queries, threshold, *, max_pairs: int = 1 << 26, return_tensors: bool = False):
+        """Every stored vector at or above a cosine ``threshold`` (a number, or one per query) for every query, exactly, under
+        the caller's ids: ``(ids (total,) int64, scores (total,) float32, bounds (q + 1,) int64)`` -
+        :func:`lshrs_amd.exact_above` over the row block where it is, superseded and erased rows left out.  What the call did
+        (pairs the first pass let through, pairs kept, launches, epsilon) is left in ``last_search_stats``."""
+        from ._exact import exact_above
+
+        return self._over_rows(exact_above, queries, threshold=threshold, max_pairs=max_pairs, return_tensors=return_tensors)
+
+    def pairs_above(self, threshold, *, max_pairs: int = 1 << 26, return_tensors: bool = False):
+        """Every pair of stored vectors at or above a cosine ``threshold`` (one number), exactly, under the caller's ids:
+        ``(ids_a (p,) int64, ids_b (p,) int64, scores (p,) float32)``, ``ids_a < ids_b``, scores descending -
+        :func:`lshrs_amd.exact_pairs_above` over the row block where it is, superseded and erased rows left out.  What the call
+        did (rows, pairs the first pass let through, pairs kept, launches, blocks, epsilon) is left in ``last_search_stats``."""
+        from ._exact import exact_pairs_above
+
+        return self._over_rows(exact_pairs_above, threshold=threshold, max_pairs=max_pairs, return_tensors=return_tensors)
+
+    def lsh_pairs_above(self, threshold, codes, offsets, members, num_bands: int, band_bytes: int, *, return_tensors: bool = False,
+                        **kwargs):
+        """The candidate pairs of ONE bucket segment (``codes``, ``offsets``, ``members``: device int64 tensors, the members
+        being ids of this store) at or above a cosine ``threshold``, under the caller's ids: ``(ids_a, ids_b, scores,
+        collisions)`` - :func:`lshrs_amd.lsh_pairs_above` over the row block where it is, the members translated to its rows
+        (``kwargs``: its ``min_collisions``, ``max_bucket``, ``max_pairs``, ``max_raw_pairs``).  A member without a stored
+        vector raises ``IndexError``.  The rows and the table are two snapshots taken one after the other, without a lock across
+        both.  What the call did is left in ``last_search_stats``."""
+        from ._join import lsh_pairs_above
+
+        return self._over_rows(lsh_pairs_above, threshold=threshold, codes=codes, offsets=offsets, members=members,
+                               num_bands=num_bands, band_bytes=band_bytes, return_tensors=return_tensors, **kwargs)
+
+    def neighbors(self, k: int = 10, *, method: str = "auto", return_tensors: bool = False):
+        """The ``k`` OTHER stored vectors nearest to every stored vector by cosine, exactly, under the caller's ids - the k-NN
+        graph of the store: ``(ids (n,) int64 ascending, neighbors (n, kk) int64, scores (n, kk) float32)``, ``kk = min(k,
+        len(self) - 1)`` - :func:`lshrs_amd.exact_knn` over the row block where it is, superseded and erased rows left out.
+        What the call did (rows, live rows, rows settled by the first pass, rows gathered, window, epsilon, chunks) is left in
+        ``last_search_stats``."""
+        from ._exact import exact_knn
+
+        return self._over_rows(exact_knn, k=k, method=method, return_tensors=return_tensors)
+
+
+class TensorRows(RowSearches):
+    """:class:`RowSearches` over a plain ``(m, dim)`` device tensor whose row ``i`` is the vector of id ``i``."""
+
+    def __init__(self, table) -> None:
+        self._table, self.dim = table, int(table.shape[1])
+        self.last_search_stats: Dict[str, Any] = {}
+
+    def _search_snapshot(self):
+        return self._table, None
+
+    def translate(self, ids_dev, err=None):
+        return ids_dev, None            # (the id is the row)
+
+
+class DeviceVectors(RowSearches):
     """Vectors of ``dim`` elements of ``dtype`` in device memory, addressed by non-negative int64 ids.
 
     ``dtype``: "float32", "bfloat16", "float16" (torch's round-to-nearest cast of the float32 rows), "int8" or
@@ -355,81 +443,6 @@ class DeviceVectors:
                         row_ids[at] = ids
                     self._row_ids = row_ids
             return rows, self._row_ids
-
-    def search(self, queries, k: int = 10, *, method: str = "auto", return_tensors: bool = False):
-        """The ``k`` stored vectors nearest to every query by cosine, exactly, under the caller's ids: ``(ids (q, kk) int64,
-        scores (q, kk) float32)``, ``kk = min(k, len(self))`` - :func:`lshrs_amd.exact_top_k` over the row block where it is,
-        superseded and erased rows left out.  What the call did (queries settled by the first pass, queries gathered, window,
-        epsilon) is left in ``last_search_stats``."""
-        from ._exact import exact_top_k
-
-        return self._search(exact_top_k, queries, k, method=method, return_tensors=return_tensors)
-
-    def search_above(self, queries, threshold, *, max_pairs: int = 1 << 26, return_tensors: bool = False):
-        """Every stored vector at or above a cosine ``threshold`` (a number, or one per query) for every query, exactly, under
-        the caller's ids: ``(ids (total,) int64, scores (total,) float32, bounds (q + 1,) int64)`` -
-        :func:`lshrs_amd.exact_above` over the row block where it is, superseded and erased rows left out.  What the call did
-        (pairs the first pass let through, pairs kept, launches, epsilon) is left in ``last_search_stats``."""
-        from ._exact import exact_above
-
-        return self._search(exact_above, queries, threshold, max_pairs=max_pairs, return_tensors=return_tensors)
-
-    def pairs_above(self, threshold, *, max_pairs: int = 1 << 26, return_tensors: bool = False):
-        """Every pair of stored vectors at or above a cosine ``threshold`` (one number), exactly, under the caller's ids:
-        ``(ids_a (p,) int64, ids_b (p,) int64, scores (p,) float32)``, ``ids_a < ids_b``, scores descending -
-        :func:`lshrs_amd.exact_pairs_above` over the row block where it is, superseded and erased rows left out.  What the call
-        did (rows, pairs the first pass let through, pairs kept, launches, blocks, epsilon) is left in ``last_search_stats``."""
-        from ._exact import exact_pairs_above
-
-        rows, row_ids = self._search_snapshot()
-        stats: Dict[str, Any] = {}
-        got = exact_pairs_above(rows, threshold, row_ids=row_ids, max_pairs=max_pairs, return_tensors=return_tensors, stats=stats)
-        self.last_search_stats = stats
-        return got
-
-    def lsh_pairs_above(self, threshold, codes, offsets, members, num_bands: int, band_bytes: int, *, return_tensors: bool = False,
-                        **kwargs):
-        """The candidate pairs of ONE bucket segment (``codes``, ``offsets``, ``members``: device int64 tensors, the members
-        being ids of this store) at or above a cosine ``threshold``, under the caller's ids: ``(ids_a, ids_b, scores,
-        collisions)`` - :func:`lshrs_amd.lsh_pairs_above` over the row block where it is, the members translated to its rows
-        (``kwargs``: its ``min_collisions``, ``max_bucket``, ``max_pairs``, ``max_raw_pairs``).  A member without a stored
-        vector raises ``IndexError``.  The rows and the table are two snapshots taken one after the other, without a lock across
-        both.  What the call did is left in ``last_search_stats``."""
-        from ._join import lsh_pairs_above
-
-        rows, row_ids = self._search_snapshot()
-        member_rows, _ = self.translate(members)
-        stats: Dict[str, Any] = {}
-        got = lsh_pairs_above(rows, threshold, codes, offsets, member_rows, num_bands, band_bytes, row_ids=row_ids,
-                              return_tensors=return_tensors, stats=stats, **kwargs)
-        self.last_search_stats = stats
-        return got
-
-    def neighbors(self, k: int = 10, *, method: str = "auto", return_tensors: bool = False):
-        """The ``k`` OTHER stored vectors nearest to every stored vector by cosine, exactly, under the caller's ids - the k-NN
-        graph of the store: ``(ids (n,) int64 ascending, neighbors (n, kk) int64, scores (n, kk) float32)``, ``kk = min(k,
-        len(self) - 1)`` - :func:`lshrs_amd.exact_knn` over the row block where it is, superseded and erased rows left out.
-        What the call did (rows, live rows, rows settled by the first pass, rows gathered, window, epsilon, chunks) is left in
-        ``last_search_stats``."""
-        from ._exact import exact_knn
-
-        rows, row_ids = self._search_snapshot()
-        stats: Dict[str, Any] = {}
-        got = exact_knn(rows, k, row_ids=row_ids, method=method, return_tensors=return_tensors, stats=stats)
-        self.last_search_stats = stats
-        return got
-
-    def _search(self, fn, queries, what, **kwargs):
-        """``fn`` (``exact_top_k`` / ``exact_above``) of ``queries`` and ``what`` (its ``k`` / ``threshold``) over one snapshot
-        of the row block and its row -> id list; what it did goes to ``last_search_stats``."""
-        shape = tuple(int(v) for v in getattr(queries, "shape", ())) or tuple(np.asarray(queries).shape)
-        if len(shape) != 2 or shape[1] != self.dim:
-            raise ValueError(f"Vectors must have shape (n, {self.dim}); received {shape}")
-        rows, row_ids = self._search_snapshot()
-        stats: Dict[str, Any] = {}
-        got = fn(queries, rows, what, row_ids=row_ids, stats=stats, **kwargs)
-        self.last_search_stats = stats
-        return got
 
     @property
     def rows(self):
