@@ -8,6 +8,8 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from tests._list_reference import S1_LIST, S1_VALUES, AUDIT_ENTRIES, AUDIT_VALUES
+
 gpu = pytest.mark.gpu
 
 
@@ -47,8 +49,8 @@ def test_rows_outside_the_guarded_range_are_flagged_wholesale_and_carry_no_stage
 
     (scratch,) = h._replay_scratch.values()                # (one stream: one list)
     k = int(st["flagged"])
-    items = scratch[0][:k].cpu().numpy()
-    y1 = scratch[5][:k].cpu().numpy()
+    items = scratch[S1_LIST][:k].cpu().numpy()
+    y1 = scratch[S1_VALUES][:k].cpu().numpy()
     rows, cols = items >> 21, items & ((1 << 21) - 1)
     key_cols = {b * 8 * h.band_bytes + j for b in range(nb) for j in range(r)}
     for row in (big, small):
@@ -79,12 +81,12 @@ def test_the_window_of_a_sampled_projection_is_the_proven_one_widened_by_a_thous
     x = torch.from_numpy(np.random.default_rng(12).standard_normal((3_000, dim)).astype(np.float32)).cuda()
     h.hash_device(x)
     (scratch,) = h._replay_scratch.values()
-    scratch[6].fill_(-1)                                  # (slots no unit of the next launch writes stay empty)
+    scratch[AUDIT_ENTRIES].fill_(-1)                                  # (slots no unit of the next launch writes stay empty)
     h.hash_device(x)
     st = dict(h.last_stats)
     assert st["route"] == "split+replay" and st["window"] == "proven" and st["audited_unflagged"] > 0, st
-    items = scratch[6].cpu().numpy()
-    vals = scratch[7].cpu().numpy().reshape(-1, 2)[:items.size]
+    items = scratch[AUDIT_ENTRIES].cpu().numpy()
+    vals = scratch[AUDIT_VALUES].cpu().numpy().reshape(-1, 2)[:items.size]
     live = items >= 0
     assert int(live.sum()) >= st["audited_unflagged"]
     rows, cols = items[live] >> 21, items[live] & ((1 << 21) - 1)

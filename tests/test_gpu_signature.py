@@ -1081,10 +1081,9 @@ def _stage1_values(torch, h, x):
     n = int(x.shape[0])
     h.stage2_sorted = False         # (the one plain list of the launch: a bucket launch keeps a segment per key column instead)
     h.hash_device(x)
-    scratch = h._replay_scratch[(x.device.index, torch.cuda.current_stream(x.device).cuda_stream)]
-    cnt = int(h.last_stats["flagged"])
-    items = scratch[0][:cnt].cpu().numpy()
-    vals = scratch[5][:cnt].cpu().numpy()
+    from tests._list_reference import stage1_list, stream_scratch
+
+    items, vals = stage1_list(stream_scratch(h, torch, x.device), int(h.last_stats["flagged"]))
     cols = 8 * h.num_bands * h.band_bytes
     y = np.full((n, cols), np.nan, dtype=np.float32)
     y[items >> 21, items & ((1 << 21) - 1)] = vals
