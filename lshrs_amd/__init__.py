@@ -12,6 +12,7 @@ compute call raises ``lshrs_amd._native.NativeLibraryError``.
 
 from ._config import HashSignatures
 from ._exact import exact_above, exact_knn, exact_pairs_above, exact_top_k, scan_epsilon, scan_max_window
+from ._groups import exact_groups_above, group_pairs, lsh_groups_above
 from ._join import lsh_pairs_above
 from ._native import NativeLibraryError
 from .bandrows import get_optimal_config
@@ -27,6 +28,6 @@ __all__ = [
     "rerank_batch", "quantize_rows", "exact_top_k", "exact_above", "exact_pairs_above", "exact_knn", "lsh_pairs_above", "scan_epsilon", "scan_max_window",
     "get_optimal_config", "InMemoryStorage", "BucketOperation", "NativeLibraryError",
     "RedisPackedWriter", "group_by_bucket", "hex_keys", "HostBlasNotRecognised",
-    "DeviceVectors",
+    "DeviceVectors", "group_pairs", "exact_groups_above", "lsh_groups_above",
 ]
 __version__ = "0.1.0"

@@ -1,5 +1,6 @@
 """ctypes binding of ``csrc/liblshrs_hip.so`` (the C ABI declared in ``include/lshrs_hip.h``, ``include/lshrs_knn.h`` and
-``include/lshrs_join.h``).
+``include/lshrs_join.h``) and of ``csrc/liblshrs_groups.so`` (``include/lshrs_groups.h``: a library of its own, loaded by
+:func:`load_groups` when the first grouping asks for it).
 
 There is no CPU implementation behind this module: if the shared library has not
 been built, or the ABI version does not match, loading raises — loudly — and so
@@ -41,8 +42,16 @@ SCAN_ELEMS = ("f32", "bf16", "f16", "i8", "f8e4m3")   # LSHRS_SCAN_F32 .. LSHRS_
 E_BADARG = -10001
 E_TOOLARGE = -10002
 
+# the second library: connected components (csrc/groups.hip, include/lshrs_groups.h) - one unit, no symbol of the first
+GROUPS_SOURCE = os.path.join(CSRC, "groups.hip")
+GROUPS_LIBRARY = os.path.join(CSRC, "liblshrs_groups.so")
+GROUPS_ABI_VERSION = 1       # LSHRS_GROUPS_ABI_VERSION
+CC_ERR_ENDPOINT = 0x1        # LSHRS_CC_ERR_ENDPOINT: an endpoint outside [0, n)
+CC_ERR_CAP = 0x2             # LSHRS_CC_ERR_CAP: a lane passed an iteration cap
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
+_groups_lib: Optional[ctypes.CDLL] = None
 
 
 class NativeLibraryError(RuntimeError):
@@ -101,6 +110,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)
             os.replace(LIBRARY + ".tmp", LIBRARY)
+        # the second library, after the first: its one unit straight into a shared object, by the same rule of staleness
+        if force or not os.path.exists(GROUPS_LIBRARY) or \
+                os.path.getmtime(GROUPS_LIBRARY) < max(os.path.getmtime(p) for p in _sources_of(GROUPS_SOURCE)):
+            cmd = [hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-I" + CSRC, "-shared", GROUPS_SOURCE, "-o", GROUPS_LIBRARY + ".tmp"]
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.run(cmd, check=True)
+            os.replace(GROUPS_LIBRARY + ".tmp", GROUPS_LIBRARY)
         return LIBRARY
 
 
@@ -404,6 +421,54 @@ def load() -> ctypes.CDLL:
                 f"{LIBRARY} is a measurement build whose keys are wrong by design (lshrs_build_flags() = {flags:#x}); "
                 "set LSHRS_ALLOW_AB=1 to load it for an A/B run, or unset LSHRS_HIP_LIBRARY")
         _lib = lib
+        return lib
+
+
+# what include/lshrs_groups.h declares: the exports of liblshrs_groups.so, all of them
+EXPORTS_GROUPS = (
+    "lshrs_groups_abi_version",
+    "lshrs_cc_init_i32",
+    "lshrs_cc_hook_i64",
+    "lshrs_cc_flatten_i32",
+)
+
+
+def load_groups() -> ctypes.CDLL:
+    """Load the library of the connected components (once).  Raises NativeLibraryError when it is not there; :func:`load`
+    neither loads it nor needs it."""
+    global _groups_lib
+    if _groups_lib is not None:
+        return _groups_lib
+    with _lock:
+        if _groups_lib is not None:
+            return _groups_lib
+        if not os.path.exists(GROUPS_LIBRARY):
+            raise NativeLibraryError(
+                f"{GROUPS_LIBRARY} is missing: the HIP extension has not been built "
+                "(run `python -c 'import __graft_entry__ as g; g.build()'`). "
+                "lshrs_amd has no CPU fallback."
+            )
+        import torch  # noqa: F401  (its libamdhip64 first, as in load())
+
+        try:
+            lib = ctypes.CDLL(GROUPS_LIBRARY)
+        except OSError as exc:  # pragma: no cover - environment specific
+            raise NativeLibraryError(f"cannot load {GROUPS_LIBRARY}: {exc}") from exc
+        for name in EXPORTS_GROUPS:
+            if not hasattr(lib, name):
+                raise NativeLibraryError(f"{GROUPS_LIBRARY} does not export {name}; rebuild it")
+        vp, i64 = ctypes.c_void_p, ctypes.c_int64
+        lib.lshrs_groups_abi_version.argtypes, lib.lshrs_groups_abi_version.restype = [], ctypes.c_int
+        # (parent, n, stream)
+        lib.lshrs_cc_init_i32.argtypes, lib.lshrs_cc_init_i32.restype = [vp, i64, vp], ctypes.c_int
+        # (a, b, n_edges, parent, n, err, stream)
+        lib.lshrs_cc_hook_i64.argtypes, lib.lshrs_cc_hook_i64.restype = [vp, vp, i64, vp, i64, vp, vp], ctypes.c_int
+        # (parent, n, err, stream)
+        lib.lshrs_cc_flatten_i32.argtypes, lib.lshrs_cc_flatten_i32.restype = [vp, i64, vp, vp], ctypes.c_int
+        got = lib.lshrs_groups_abi_version()
+        if got != GROUPS_ABI_VERSION:
+            raise NativeLibraryError(f"{GROUPS_LIBRARY} has ABI version {got}, expected {GROUPS_ABI_VERSION}; rebuild it")
+        _groups_lib = lib
         return lib
 
 

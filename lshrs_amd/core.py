@@ -52,6 +52,15 @@ __all__ = ["LSHRS", "lshrs"]
 
 _FORMAT_VERSION = "0.1.1a4"  # on-disk format version string the reference writes (main.py:882)
 _ZERO_MSG = "Cannot index zero vector - norm undefined. Check embeddings for corruption."
+# what pairs_above / groups_above leave in last_search_stats for an index without buckets: the join's counts, all zero
+_EMPTY_JOIN_STATS = {"buckets": 0, "skipped_buckets": 0, "raw_pairs": 0, "emitted": 0, "kept": 0, "launches": 0}
+
+
+def _group_lists(members: np.ndarray, offsets: np.ndarray) -> List[List[int]]:
+    """``(members, offsets)`` of a grouping as one list of ids per group."""
+    with _gc_paused():
+        flat, at = members.tolist(), offsets.tolist()
+        return [flat[lo:hi] for lo, hi in zip(at[:-1], at[1:])]
 
 
 def _device_tensor(obj):
@@ -747,26 +756,87 @@ class LSHRS:
         raises; an empty index gives an empty answer.  ``last_search_stats`` receives ``buckets``, ``skipped_buckets``,
         ``raw_pairs`` (pairs the counted buckets hold, with repetitions), ``emitted`` (distinct candidate pairs), ``kept``,
         ``launches`` (emit launches), ``segments_folded`` and ``fold_ms``."""
-        from . import _join
-
-        nb, bb = int(self._config["num_bands"]), int(self._hasher.band_bytes)
-        _join.check_join_args(threshold, min_collisions, max_bucket, max_pairs, nb)
-        kw = {"min_collisions": int(min_collisions), "max_bucket": max_bucket, "max_pairs": int(max_pairs)}
-        fold: Dict[str, Any] = {}
-        over = self._searched("pairs_above")
-        seg = self._join_segment(over._search_snapshot()[0].device, bb, fold)
-        if fold.pop("empty"):                       # (no segment: an empty index)
+        over, seg, fold, shape, kw = self._join_plan("pairs_above", threshold, min_collisions, max_bucket, max_pairs)
+        if seg is None:                             # (no segment: an empty index)
             ids_a, ids_b, scores, collisions = (np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.float32),
                                                 np.empty(0, np.int32))
-            self.last_search_stats = {"buckets": 0, "skipped_buckets": 0, "raw_pairs": 0, "emitted": 0, "kept": 0, "launches": 0}
+            self.last_search_stats = dict(_EMPTY_JOIN_STATS)
         else:
-            ids_a, ids_b, scores, collisions = over.lsh_pairs_above(threshold, *seg, nb, bb, **kw)
+            ids_a, ids_b, scores, collisions = over.lsh_pairs_above(threshold, *seg, *shape, **kw)
             self.last_search_stats = dict(over.last_search_stats)
         self.last_search_stats.update(fold)
         if return_arrays:
             return ids_a, ids_b, scores, collisions
         with _gc_paused():
             return list(zip(ids_a.tolist(), ids_b.tolist(), scores.astype(np.float64).tolist(), collisions.tolist()))
+
+    def _join_plan(self, caller: str, threshold, min_collisions, max_bucket, max_pairs):
+        """What :meth:`pairs_above` and :meth:`groups_above` do before their join: the arguments checked on the host, the rows
+        that are searched, the store's buckets as one segment.  Returns ``(rows, segment or None for an empty index, fold
+        stats, (num_bands, band_bytes), keywords of the join)``."""
+        from . import _join
+
+        nb, bb = int(self._config["num_bands"]), int(self._hasher.band_bytes)
+        _join.check_join_args(threshold, min_collisions, max_bucket, max_pairs, nb)
+        kw = {"min_collisions": int(min_collisions), "max_bucket": max_bucket, "max_pairs": int(max_pairs)}
+        fold: Dict[str, Any] = {}
+        over = self._searched(caller)
+        seg = self._join_segment(over._search_snapshot()[0].device, bb, fold)
+        if fold.pop("empty"):
+            seg = None
+        return over, seg, fold, (nb, bb), kw
+
+    def groups_exact_above(self, threshold, *, return_arrays: bool = False):
+        """The near-duplicate GROUPS among what is indexed at a cosine ``threshold`` (one number), EXACTLY: the connected
+        components of the pairs of :meth:`pairs_exact_above`, computed on the device (``lshrs_amd.exact_groups_above``), over
+        the same corpus and with the same errors where there is none.  A group is a connected component of "score >=
+        threshold" - SINGLE LINKAGE: two members of one group are joined by a chain of pairs at or above the threshold and may
+        score below it against each other.  Returns ``[[id, ...], ...]``: groups by ascending smallest id, ids ascending
+        inside a group, only ids that are in some pair - the first id of every group is the one to keep, and dropping the
+        others is a deduplication - or ``(members (v,) int64, offsets (g + 1,) int64)`` with ``return_arrays``.
+        ``last_search_stats`` tells what the call did (the join's counts, ``pairs``, ``grouped``, ``groups``, ``largest``)."""
+        over = self._searched("groups_exact_above")
+        members, offsets = over.groups_above(threshold)
+        self.last_search_stats = dict(over.last_search_stats)
+        return (members, offsets) if return_arrays else _group_lists(members, offsets)
+
+    def groups_above(self, threshold, *, min_collisions: int = 1, max_bucket: Optional[int] = None, max_pairs: int = 1 << 26,
+                     return_arrays: bool = False):
+        """The near-duplicate GROUPS the index holds IN ITS BUCKETS at a cosine ``threshold``: the connected components of the
+        pairs of :meth:`pairs_above` with the same arguments, computed on the device (``lshrs_amd.lsh_groups_above``) - the
+        approximate counterpart of :meth:`groups_exact_above`.  A group is a connected component - SINGLE LINKAGE: two members
+        of one group may neither share a bucket nor reach the threshold against each other.  The pairs are a subset of
+        :meth:`pairs_exact_above`'s, so every group lies inside ONE group of :meth:`groups_exact_above`: the buckets split
+        groups, they never merge them.  Returns ``[[id, ...], ...]`` as :meth:`groups_exact_above` does (the first id of a
+        group is its smallest id, the one to keep), or ``(members, offsets)`` with ``return_arrays``; an empty index gives
+        ``[]``.  The store, the errors and the two snapshots: as for
+        :meth:`pairs_above`.  ``last_search_stats`` receives what :meth:`pairs_above` leaves there and ``pairs``, ``grouped``,
+        ``groups``, ``largest``."""
+        over, seg, fold, shape, kw = self._join_plan("groups_above", threshold, min_collisions, max_bucket, max_pairs)
+        if seg is None:
+            members, offsets = np.empty(0, np.int64), np.zeros(1, np.int64)
+            self.last_search_stats = dict(_EMPTY_JOIN_STATS, pairs=0, grouped=0, groups=0, largest=0)
+        else:
+            members, offsets = over.lsh_groups_above(threshold, *seg, *shape, **kw)
+            self.last_search_stats = dict(over.last_search_stats)
+        self.last_search_stats.update(fold)
+        return (members, offsets) if return_arrays else _group_lists(members, offsets)
+
+    def recall_groups_above(self, threshold) -> Dict[str, Any]:
+        """How much of the exact grouping the index recovers, measured as the duplicates a deduplication would remove: the
+        truth is :meth:`groups_exact_above` ``(threshold)``, what the index finds is :meth:`groups_above` ``(threshold)``,
+        whose groups refine the truth's.  Returns ``groups`` / ``truth_groups``, ``removable`` (the sum over the LSH groups
+        of ``size - 1``: the ids that go when one per group is kept) / ``truth_removable`` (the same over the exact groups),
+        ``recall = removable / truth_removable`` (at most 1; 1.0 when there is no truth) and ``largest`` /
+        ``truth_largest``.  ``last_search_stats`` is that of the :meth:`groups_above` call."""
+        t_members, t_offsets = self.groups_exact_above(threshold, return_arrays=True)
+        members, offsets = self.groups_above(threshold, return_arrays=True)
+        groups, truth_groups = int(offsets.shape[0]) - 1, int(t_offsets.shape[0]) - 1
+        removable, truth_removable = int(members.shape[0]) - groups, int(t_members.shape[0]) - truth_groups
+        return {"groups": groups, "truth_groups": truth_groups, "removable": removable, "truth_removable": truth_removable,
+                "recall": removable / truth_removable if truth_removable else 1.0,
+                "largest": int(np.diff(offsets).max()) if groups else 0,
+                "truth_largest": int(np.diff(t_offsets).max()) if truth_groups else 0}
 
     def _join_segment(self, dev, band_bytes: int, fold: Dict[str, Any]):
         """The store's bucket arrays as ONE segment on ``dev`` - ``(codes, offsets, members)`` int64 tensors, None for an empty

@@ -54,7 +54,7 @@ def check_ids(ids) -> np.ndarray:
 
 
 class RowSearches:
-    """The five searches over device-resident rows under ids - the route from whatever holds such rows to ``_exact`` /
+    """The seven searches over device-resident rows under ids - the route from whatever holds such rows to ``_exact`` /
     ``_join``.  The holder supplies ``dim``, ``_search_snapshot() -> (rows, row_ids)`` (``row_ids``: the id of every row,
     negative where it has none; None where the id is the row) and ``translate(ids) -> (rows of those ids, ...)``; it
     receives ``last_search_stats``: what the last search that returned did."""
@@ -114,6 +114,28 @@ class RowSearches:
         from ._join import lsh_pairs_above
 
         return self._over_rows(lsh_pairs_above, threshold=threshold, codes=codes, offsets=offsets, members=members,
+                               num_bands=num_bands, band_bytes=band_bytes, return_tensors=return_tensors, **kwargs)
+
+    def groups_above(self, threshold, *, max_pairs: int = 1 << 26, return_tensors: bool = False):
+        """The near-duplicate GROUPS among the stored vectors at a cosine ``threshold``, exactly, under the caller's ids:
+        ``(members (v,) int64, offsets (g + 1,) int64)`` - the connected components of :meth:`pairs_above`'s pairs
+        (:func:`lshrs_amd.exact_groups_above` over the row block where it is; single linkage: two members of one group may
+        score below the threshold against each other).  Groups by ascending smallest id, members ascending: the first member
+        of every group is the one to keep.  What the call did (the join's counts, pairs, ids grouped, groups, the largest
+        group) is left in ``last_search_stats``."""
+        from ._groups import exact_groups_above
+
+        return self._over_rows(exact_groups_above, threshold=threshold, max_pairs=max_pairs, return_tensors=return_tensors)
+
+    def lsh_groups_above(self, threshold, codes, offsets, members, num_bands: int, band_bytes: int, *, return_tensors: bool = False,
+                         **kwargs):
+        """The near-duplicate GROUPS ONE bucket segment holds at a cosine ``threshold``, under the caller's ids: ``(members,
+        offsets)`` - the connected components of :meth:`lsh_pairs_above`'s pairs with the same arguments
+        (:func:`lshrs_amd.lsh_groups_above` over the row block where it is; every group lies inside one group of
+        :meth:`groups_above`).  What the call did is left in ``last_search_stats``."""
+        from ._groups import lsh_groups_above
+
+        return self._over_rows(lsh_groups_above, threshold=threshold, codes=codes, offsets=offsets, members=members,
                                num_bands=num_bands, band_bytes=band_bytes, return_tensors=return_tensors, **kwargs)
 
     def neighbors(self, k: int = 10, *, method: str = "auto", return_tensors: bool = False):
