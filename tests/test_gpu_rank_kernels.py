@@ -11,6 +11,7 @@ import math
 import numpy as np
 import pytest
 
+from tests._plumbing_reference import rank_model as _rank_model, special_scores as _special_scores
 from tests._ranking import literal_lists
 
 pytestmark = pytest.mark.gpu
@@ -40,18 +41,6 @@ def _ptr(t):
 # the models
 # ------------------------------------------------------------------------------------------------------------------
 
-def _rank_model(scores):
-    """Positions of `scores` in the header's order: descending score; ties by ascending position; NaN last, by position;
-    +0.0 ahead of -0.0 wherever they stand."""
-    def key(p):
-        v = float(scores[p])
-        if v != v:
-            return (1, 0.0, 0, p)
-        return (0, -v, int(np.signbit(scores[p])) if v == 0.0 else 0, p)
-
-    return sorted(range(len(scores)), key=key)
-
-
 def _keep_model(n, top_k, top_p):
     """lshrs_query_scan_i32's cut: 0 for no candidates; top_p < 0: min(n, top_k) (top_k < 0: n); else
     min(max(1, ceil((double)n * top_p)), top_k)."""
@@ -59,20 +48,6 @@ def _keep_model(n, top_k, top_p):
         return 0
     k = n if top_p < 0 else min(n, max(1, math.ceil(n * top_p)))
     return k if top_k < 0 else min(k, top_k)
-
-
-def _special_scores(rng, n):
-    """Quarter steps in [-1.5, 1.5] - thirteen values, so runs of exact ties at every length - and, where they fit: a -0.0 AHEAD
-    of a +0.0, three NaNs (one with the sign bit and a payload), +inf and -inf."""
-    s = (rng.integers(-6, 7, size=n) / 4.0).astype(np.float32)
-    neg_nan = np.array([0xFFC00001], dtype=np.uint32).view(np.float32)[0]
-    specials = [np.float32(-0.0), np.float32(0.0), np.float32(np.nan), np.float32(np.inf), np.float32(-np.inf), neg_nan,
-                np.float32(np.nan)][:n]
-    pos = np.sort(rng.choice(n, size=len(specials), replace=False)) if n else np.empty(0, np.int64)
-    rest = rng.permutation(pos[2:])
-    for p, v in zip(np.r_[pos[:2], rest].astype(np.int64), specials):
-        s[p] = v
-    return s
 
 
 def _same_f32(got, want):
