@@ -310,6 +310,41 @@ int lshrs_sig_project_f32(const float* X, int64_t n, int64_t ldx,
                           const void* workspace, int32_t num_bands, int32_t rows_per_band, int32_t dim,
                           float* Y, int64_t ldy, void* stream);
 
+/* Diagnostic twin of the REPLAY (additive to ABI 7): lshrs_sig_project_f32 lets the f32 chain's value out, this entry the
+ * value the device computes when it replays the host BLAS's summation order - `yb`, whose sign patches the key - from the very
+ * kernels the product runs (a pointer that is NULL on every product path, no instantiation of its own), through the
+ * product's own choice of kernel.  The tests compare it bit for bit with lshrs_tb_model_row_dot (lshrs_host.h).
+ *   route  LSHRS_REPLAY_ROUTE_STAGE2  stage 2 of lshrs_sig_hash_batch_split_replay_f32 without its stage 1: the refusals of that
+ *            entry, then the kernel, slab and grid it picks (LDS-DMA form, its short-row and GENERAL variants, the plain-load
+ *            form for bands of one row).  `list`: entries (row << 21) | padded key column, as stage 1 writes them.  Or
+ *            `sort` (and list == NULL): the column segments of lshrs_sig_sort as stage 1 fills them - list[column * (cap /
+ *            columns) + i], hist[parity * 1024 + column] = entries wanted -, which takes the bucket form; the scratch must be
+ *            one that pass itself would use (mode 1, thr given, at most 1024 padded key columns, more than four k-tiles,
+ *            bands of two rows and more, cap / columns >= 64), else LSHRS_E_BADARG.  Every entry of a segment carries that
+ *            segment's column (a group of eight fetches ONE hyperplane between its lanes).  Entries with bit 62 (the audit
+ *            sample) are compared, not patched, and get no value.
+ *          LSHRS_REPLAY_ROUTE_TIES    the replay of lshrs_sig_resolve_ties_replay_f32 (its refusals, its choice between the
+ *            LDS-DMA and the plain-load form) on `list`, in the same entry format, instead of an expanded tie list.
+ *          LSHRS_REPLAY_ROUTE_SMALL   lshrs_sig_hash_small_replay_f32 (its refusals, its kernel ladder): no list.
+ *   keys     patched (stage 2, ties: the listed bits, by 32-bit atomics) or written (small) exactly as the product does.
+ *   values   stage 2, ties: float[list_cap] - values[e] = the value of list entry e; with `sort`: float[cap], at the entry's
+ *            position in the segments.  Written for live entries only (e < the count, column < 8 x key bytes per row, not
+ *            an audit entry); everything else is left as it was.  small: float (n, 8 x key bytes per row), every column.
+ *   counters DEVICE int32[LSHRS_SIG_DEVICE_COUNTERS]; stage 2, ties: [1] = the number of entries in `list` ON ENTRY (what
+ *            stage 1 leaves there), every other word zero; on return the folded counters stay in the block ([3] bits changed,
+ *            [7] != 0: a column of the segments wanted more than its share - the entries beyond it were not taken).
+ *            small: [0] only grows (the tie count).
+ * Precondition the library cannot check on a device list: every entry's row is < n.  Nothing is launched when the call
+ * returns an error. */
+#define LSHRS_REPLAY_ROUTE_STAGE2 0
+#define LSHRS_REPLAY_ROUTE_TIES   1
+#define LSHRS_REPLAY_ROUTE_SMALL  2
+int lshrs_sig_replay_values_f32(const float* X, int64_t n, int64_t ldx,
+                                const void* workspace, int32_t num_bands, int32_t rows_per_band, int32_t dim,
+                                int32_t blas_model, int32_t route, uint8_t* keys, float* values,
+                                int64_t* list, int32_t list_cap, const lshrs_sig_sort* sort,
+                                int32_t* counters, void* stream);
+
 /* Column count (multiple of 32) of the Y matrix lshrs_sig_project_f32 writes. */
 int32_t lshrs_sig_padded_columns(int32_t num_bands, int32_t rows_per_band);
 

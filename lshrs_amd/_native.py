@@ -39,6 +39,8 @@ BUILD_TUNED = 0x2        # LSHRS_BUILD_TUNED
 
 SCAN_ELEMS = ("f32", "bf16", "f16", "i8", "f8e4m3")   # LSHRS_SCAN_F32 .. LSHRS_SCAN_F8E4M3, in that order
 
+REPLAY_ROUTE_STAGE2, REPLAY_ROUTE_TIES, REPLAY_ROUTE_SMALL = 0, 1, 2     # LSHRS_REPLAY_ROUTE_* (lshrs_sig_replay_values_f32)
+
 E_BADARG = -10001
 E_TOOLARGE = -10002
 
@@ -163,6 +165,9 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.lshrs_wait_done.restype = c.c_int
     lib.lshrs_sig_project_f32.argtypes = [vp, i64, i64, vp, i32, i32, i32, vp, i64, vp]
     lib.lshrs_sig_project_f32.restype = c.c_int
+    # (X, n, ldx, workspace, bands, rows, dim, blas_model, route, keys, values, list, list_cap, sort, counters, stream)
+    lib.lshrs_sig_replay_values_f32.argtypes = [vp, i64, i64, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp]
+    lib.lshrs_sig_replay_values_f32.restype = c.c_int
     lib.lshrs_gather_rows_f32.argtypes = [vp, i64, i32, vp, i64, vp, vp]
     lib.lshrs_gather_rows_f32.restype = c.c_int
     lib.lshrs_gather_tied_rows_f32.argtypes = [vp, i64, i32, vp, vp, i32, vp, vp]
@@ -306,6 +311,7 @@ EXPORTS = (
     "lshrs_stream_synchronize",
     "lshrs_wait_done",
     "lshrs_sig_project_f32",
+    "lshrs_sig_replay_values_f32",
     "lshrs_gather_rows_f32",
     "lshrs_gather_tied_rows_f32",
     "lshrs_scatter_band_keys_u8",

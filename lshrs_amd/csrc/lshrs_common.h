@@ -464,6 +464,9 @@ struct FixArgs {
   int col_cap;
   const float* flag_thr;
   int* overflow;
+  // NULL on every product path.  lshrs_sig_replay_values_f32 (the tests' entry): the replayed value of every live, non-audit entry -
+  // the one whose sign patches the key -, at the entry's position in the list (SAMEP buckets: in the column segments)
+  float* replay_y;
 };
 constexpr int kFixParts = 6;
 
@@ -629,6 +632,13 @@ LSHRS_HIDDEN int lshrs_launch_sig16(const lshrs::SigArgs& a, unsigned grid, bool
 LSHRS_HIDDEN int lshrs_launch_sig16r(const lshrs::SigArgs& a, int nct, int kt, unsigned grid, unsigned block, hipStream_t s,
                                      hipEvent_t start, hipEvent_t stop);
 LSHRS_HIDDEN int lshrs_replay_stage2(const lshrs::FixArgs& f, int32_t* counters, int32_t* host_counts, const lshrs::Opts& o, hipStream_t s);
+LSHRS_HIDDEN int lshrs_small_replay(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands, int32_t rows_per_band,
+                                    int32_t dim, uint8_t* keys, uint8_t* row_flags, int32_t* counters, float tau, int32_t blas_model,
+                                    int32_t* host_done, int32_t epoch, float* values, void* stream);      // sig_small.hip
+LSHRS_HIDDEN int lshrs_split_stage2_args(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands, int32_t rows_per_band,
+                                         int32_t dim, uint8_t* keys, int32_t* counters, float tau, int64_t* flag_list, float* flag_y,
+                                         int32_t flag_cap, int32_t blas_model, const lshrs::Opts& o, bool want_buckets,
+                                         lshrs::FixArgs* out);                                             // sig_split.hip
 LSHRS_HIDDEN int lshrs_sort_u64_rows(uint64_t* items, int q, int64_t cpad, hipStream_t s);     // rerank.hip: K3's global network
 LSHRS_HIDDEN uint32_t lshrs_flags_sig16(void);
 LSHRS_HIDDEN uint32_t lshrs_flags_sig16r(void);

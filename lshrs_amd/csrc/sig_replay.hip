@@ -359,6 +359,7 @@ __global__ __launch_bounds__(64) void sig_fix8_kernel(const FixArgs a) {
         }
       }
     }
+    if (REPLAY && a.replay_y != nullptr) a.replay_y[e] = yb;   // (lshrs_sig_replay_values_f32 only: the value itself, for the tests)
     }   // sub == 0 && live
     if (!has_next) break;
     cur = nxt;
@@ -631,6 +632,7 @@ __global__ __launch_bounds__(64) void sig_fixany_kernel(const FixArgs a) {
         if (want) atomicOr(w32, bitmask);
         else atomicAnd(w32, ~bitmask);
       }
+      if (a.replay_y != nullptr) a.replay_y[e] = y;                // (lshrs_sig_replay_values_f32 only: the value itself, for the tests)
     }
   }
 #pragma unroll
@@ -810,22 +812,16 @@ int lshrs_replay_stage2(const FixArgs& f, int32_t* counters, int32_t* host_count
   return -(int)hipGetLastError();
 }
 
-extern "C" {
-
-int lshrs_sig_resolve_ties_replay_f32(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands,
-                                       int32_t rows_per_band, int32_t dim, uint8_t* keys, const int64_t* tie_list,
-                                       int32_t tie_cap, int32_t* counters, float tau, int64_t* flag_list,
-                                       int32_t flag_cap, int32_t blas_model, int32_t* host_counts, void* stream) {
-  int32_t* tie_count = counters;                          // [0] tie entries the f32 kernel wanted to write
-  int32_t* flag_count = counters != nullptr ? counters + 1 : nullptr;   // [1] items expanded from them
-  if (n == 0) return 0;
-  if (X == nullptr || workspace == nullptr || keys == nullptr || tie_list == nullptr || tie_count == nullptr ||
-      flag_list == nullptr || flag_count == nullptr || tie_cap <= 0 || flag_cap <= 0 || n < 0 || ldx < dim ||
+// The replay behind the f32 kernel: what it refuses and which form takes the list - lshrs_sig_resolve_ties_replay_f32 and the route
+// of lshrs_sig_replay_values_f32 that stands for it.  lists_ok: the caller's own lists and capacities are there.
+struct TiesPlan { SigGeom g; int row_bytes; bool plain; };      // plain: sig_fixany_kernel, else the LDS-DMA form
+static int ties_replay_plan(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands, int32_t rows_per_band, int32_t dim,
+                            const uint8_t* keys, bool lists_ok, int32_t blas_model, TiesPlan* p) {
+  if (X == nullptr || workspace == nullptr || keys == nullptr || !lists_ok || n < 0 || ldx < dim ||
       !sig_shape_ok(num_bands, rows_per_band, dim) || (blas_model != 1 && blas_model != 2 && blas_model != 3) ||
       (blas_model == 3 && (dim > 8 || rows_per_band < 2)))     // (model 3: the SkylakeX build's small-matrix kernels only)
     return LSHRS_E_BADARG;
   const SigGeom g = sig_geom(num_bands, rows_per_band, dim);
-  const int row_bytes = num_bands * g.bb;
   // stage 2 stages 16-byte chunks of 16-byte aligned rows (key rows may have any width: split_pass's comment); anything
   // else - dim % 4 elements of scalar tail (blas_model 1 / 2: how the host compiles it), rows that are only 4-byte aligned -
   // goes through the plain-load form of the same replay (sig_fixany_kernel)
@@ -840,26 +836,88 @@ int lshrs_sig_resolve_ties_replay_f32(const float* X, int64_t n, int64_t ldx, co
   if (!one_row && dim < 9 && dim % 4 != 0 && blas_model == 1) return LSHRS_E_TOOLARGE;
   const bool short_last_block = body % 8 != 0 && body > 4096;
   if (n >= ((int64_t)1 << 42) || (fast && !short_last_block && blas_model != 1)) return LSHRS_E_TOOLARGE;
+  *p = TiesPlan{g, num_bands * g.bb, !fast || short_last_block};
+  return 0;
+}
+
+// ... and its launches: the list of f (the count on the device), then the fold of the statistics
+static void ties_replay_launch(FixArgs& f, const TiesPlan& p, int32_t* counters, int32_t* host_counts, hipStream_t s) {
+  f.partials = counters + LSHRS_SIG_COUNTERS;
+  const int64_t groups = ((int64_t)f.flag_cap + kFixG - 1) / kFixG;
+  const dim3 grid((unsigned)(groups < kFixGridG ? groups : kFixGridG)), block(64);
+  f.tail_model = f.blas_model;
+  if (p.plain) hipLaunchKernelGGL(sig_fixany_kernel, grid, block, 0, s, f);
+  else launch_replay<kFixSlabG, false>(blas_general(f.rows_per_band, p.g.ktiles, f.dim), grid, f, s, nullptr, nullptr);
+  hipLaunchKernelGGL(export_counts_kernel, dim3(1), dim3(kExportThreads), 0, s, counters, host_counts, (int)grid.x);
+}
+
+extern "C" {
+
+int lshrs_sig_resolve_ties_replay_f32(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands,
+                                       int32_t rows_per_band, int32_t dim, uint8_t* keys, const int64_t* tie_list,
+                                       int32_t tie_cap, int32_t* counters, float tau, int64_t* flag_list,
+                                       int32_t flag_cap, int32_t blas_model, int32_t* host_counts, void* stream) {
+  int32_t* tie_count = counters;                          // [0] tie entries the f32 kernel wanted to write
+  int32_t* flag_count = counters != nullptr ? counters + 1 : nullptr;   // [1] items expanded from them
+  if (n == 0) return 0;
+  TiesPlan p;
+  const int rc = ties_replay_plan(X, n, ldx, workspace, num_bands, rows_per_band, dim, keys,
+                                  tie_list != nullptr && tie_count != nullptr && flag_list != nullptr && tie_cap > 0 && flag_cap > 0,
+                                  blas_model, &p);
+  if (rc != 0) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const float* base = static_cast<const float*>(workspace);
   {
     const int threads = 256;
     const int blocks = tie_cap < 256 * 64 ? (tie_cap + threads - 1) / threads : 64;
     hipLaunchKernelGGL(expand_ties_kernel, dim3((unsigned)blocks), dim3(threads), 0, s, tie_list, tie_count, tie_cap,
-                       row_bytes * 8, flag_list, flag_cap, flag_count);
+                       p.row_bytes * 8, flag_list, flag_cap, flag_count);
   }
   // (no tie list: the caller has the number of tie entries already; stage 2 only decides them)
-  FixArgs f = fix_args_base(X, ldx, dim, base, g, rows_per_band, keys, row_bytes, flag_list, flag_count, flag_cap, tau, blas_model);
-  f.partials = counters + LSHRS_SIG_COUNTERS;
-  {
-    const int64_t groups = ((int64_t)flag_cap + kFixG - 1) / kFixG;
-    const dim3 grid((unsigned)(groups < kFixGridG ? groups : kFixGridG)), block(64);
-    f.tail_model = blas_model;
-    if (!fast || short_last_block) hipLaunchKernelGGL(sig_fixany_kernel, grid, block, 0, s, f);
-    else launch_replay<kFixSlabG, false>(blas_general(rows_per_band, g.ktiles, dim), grid, f, s, nullptr, nullptr);
-    hipLaunchKernelGGL(export_counts_kernel, dim3(1), dim3(kExportThreads), 0, s, counters, host_counts, (int)grid.x);
-  }
+  FixArgs f = fix_args_base(X, ldx, dim, base, p.g, rows_per_band, keys, p.row_bytes, flag_list, flag_count, flag_cap, tau, blas_model);
+  ties_replay_launch(f, p, counters, host_counts, s);
   return -(int)hipGetLastError();
+}
+
+int lshrs_sig_replay_values_f32(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands,
+                                int32_t rows_per_band, int32_t dim, int32_t blas_model, int32_t route, uint8_t* keys,
+                                float* values, int64_t* list, int32_t list_cap, const lshrs_sig_sort* sort,
+                                int32_t* counters, void* stream) {
+  if (n == 0) return 0;
+  if (values == nullptr || counters == nullptr) return LSHRS_E_BADARG;
+  constexpr float kValuesTau = 8 * 0x1p-24f;      // (the tie window feeds a statistic only: no key bit and no value depends on it)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (route == LSHRS_REPLAY_ROUTE_SMALL) {
+    if (list != nullptr || sort != nullptr) return LSHRS_E_BADARG;
+    return lshrs_small_replay(X, n, ldx, workspace, num_bands, rows_per_band, dim, keys, nullptr, counters, kValuesTau, blas_model,
+                              nullptr, 0, values, stream);
+  }
+  if (route == LSHRS_REPLAY_ROUTE_TIES) {
+    TiesPlan p;
+    const int rc = ties_replay_plan(X, n, ldx, workspace, num_bands, rows_per_band, dim, keys, list != nullptr && list_cap > 0 && sort == nullptr,
+                                    blas_model, &p);
+    if (rc != 0) return rc;
+    FixArgs f = fix_args_base(X, ldx, dim, static_cast<const float*>(workspace), p.g, rows_per_band, keys, p.row_bytes, list, counters + 1,
+                              list_cap, kValuesTau, blas_model);
+    f.replay_y = values;
+    ties_replay_launch(f, p, counters, nullptr, s);
+    return -(int)hipGetLastError();
+  }
+  if (route != LSHRS_REPLAY_ROUTE_STAGE2) return LSHRS_E_BADARG;
+  Opts o;
+  if (sort != nullptr) {            // the column segments: what read_opts asks of the scratch, and no list beside it
+    if (list != nullptr || sort->struct_bytes < sizeof(lshrs_sig_sort) || sort->list == nullptr || sort->y == nullptr || sort->hist == nullptr ||
+        sort->cap <= 0)
+      return LSHRS_E_BADARG;
+    o.sort = sort;
+  }
+  FixArgs f;
+  const int rc = lshrs_split_stage2_args(X, n, ldx, workspace, num_bands, rows_per_band, dim, keys, counters, kValuesTau,
+                                         sort != nullptr ? sort->list : list, nullptr, sort != nullptr ? sort->cap : list_cap, blas_model, o,
+                                         sort != nullptr, &f);
+  if (rc != 0) return rc;
+  f.replay_y = values;
+  return lshrs_replay_stage2(f, counters, nullptr, o, s);
 }
 
 }  // extern "C"

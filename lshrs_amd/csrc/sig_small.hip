@@ -39,6 +39,7 @@ struct SmallArgs {
   int rows_per_band;      // (which of the library's kernels computes a column: blas_row_kind)
   int band_cols;
   int dim;                // (GENERAL: rows that are not whole k-tiles - X is readable, not used, up to 32 * ktiles per row)
+  float* values;          // NULL in product.  lshrs_sig_replay_values_f32 (the tests' entry): (n, 8 * row_bytes), every column's replayed value
 };
 
 template <int KT, bool GENERAL>
@@ -111,6 +112,7 @@ __global__ __launch_bounds__(64) void sig_small_kernel(const SmallArgs a) {
   float m2 = __builtin_fmaxf(am, __shfl(am, (lane + 32) & 63));
   m2 = __builtin_fmaxf(m2, __shfl(m2, (lane + 8) & 63));
   m2 = __builtin_fmaxf(m2, __shfl(m2, (lane + 16) & 63));
+  if (a.values != nullptr && sub == 0) a.values[(int64_t)row * 8 * a.row_bytes + col] = yb;
   const bool want = sub == 0 && yb > 0.f;                          // (0, -0 and NaN give 0: lsh.py:204)
   const bool tie = sub == 0 && __builtin_fabsf(yb) < a.tau * sqrtf(s2) * a.norms[col];
   const unsigned bits = (unsigned)(__ballot(want) & 0xffull);      // lane g = bit g of the byte
@@ -139,12 +141,11 @@ __global__ __launch_bounds__(64) void sig_small_kernel(const SmallArgs a) {
 }
 }  // namespace
 
-extern "C" {
-
-int lshrs_sig_hash_small_replay_f32(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands,
-                                    int32_t rows_per_band, int32_t dim, uint8_t* keys, uint8_t* row_flags,
-                                    int32_t* counters, float tau, int32_t blas_model, int32_t* host_done, int32_t epoch,
-                                    void* stream) {
+// The checks and the KT / GENERAL ladder of lshrs_sig_hash_small_replay_f32, stated once: that entry (values = NULL) and the small
+// route of lshrs_sig_replay_values_f32 (sig_replay.hip), which also wants every column's replayed value.
+int lshrs_small_replay(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands, int32_t rows_per_band,
+                       int32_t dim, uint8_t* keys, uint8_t* row_flags, int32_t* counters, float tau, int32_t blas_model,
+                       int32_t* host_done, int32_t epoch, float* values, void* stream) {
   if (n == 0) return 0;
   if (X == nullptr || workspace == nullptr || keys == nullptr || counters == nullptr || n < 0 || ldx < dim ||
       !sig_shape_ok(num_bands, rows_per_band, dim) || blas_model != 1)
@@ -175,6 +176,7 @@ int lshrs_sig_hash_small_replay_f32(const float* X, int64_t n, int64_t ldx, cons
   a.rows_per_band = rows_per_band;
   a.band_cols = 8 * g.bb;
   a.dim = dim;
+  a.values = values;
   const dim3 grid((unsigned)(n * row_bytes)), block(64);
   if (!blas_general(rows_per_band, g.ktiles, dim)) {
     if (g.ktiles <= 24) hipLaunchKernelGGL((sig_small_kernel<24, false>), grid, block, 0, s, a);
@@ -186,6 +188,16 @@ int lshrs_sig_hash_small_replay_f32(const float* X, int64_t n, int64_t ldx, cons
     else hipLaunchKernelGGL((sig_small_kernel<128, true>), grid, block, 0, s, a);
   }
   return -(int)hipGetLastError();
+}
+
+extern "C" {
+
+int lshrs_sig_hash_small_replay_f32(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands,
+                                    int32_t rows_per_band, int32_t dim, uint8_t* keys, uint8_t* row_flags,
+                                    int32_t* counters, float tau, int32_t blas_model, int32_t* host_done, int32_t epoch,
+                                    void* stream) {
+  return lshrs_small_replay(X, n, ldx, workspace, num_bands, rows_per_band, dim, keys, row_flags, counters, tau, blas_model, host_done,
+                            epoch, nullptr, stream);
 }
 
 }  // extern "C"

@@ -65,18 +65,31 @@ static bool sig16_half_rows(int ktiles, int64_t groups_of_256) {
   return ktiles <= kHalfMaxTiles || groups_of_256 <= kHalfMaxGroups;
 }
 
-static int split_pass(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands,
-                      int32_t rows_per_band, int32_t dim, uint8_t* keys, int64_t* tie_list, int32_t tie_cap,
-                      int32_t* tie_count, float tau, uint8_t* row_flags, int64_t* flag_list, float* flag_y,
-                      int32_t flag_cap, int32_t* flag_count, float tau1, int blas_model, int32_t* counters,
-                      int32_t* host_counts, const lshrs_sig_audit* audit, const lshrs_sig_opts* opts, void* stream) {
-  if (n == 0) return 0;
+// What lshrs_sig_hash_batch_split_replay_f32 refuses before split_pass sees the call (and lshrs_split_stage2_args with it)
+static int split_replay_refusal(int32_t num_bands, int32_t rows_per_band, int32_t dim, int32_t blas_model, const int32_t* counters) {
+  const bool resident = sig_resident(num_bands, rows_per_band, dim).on;
+  // dim % 4 elements of scalar tail: modelled from 9 elements up, model 1 / 2 = how the build compiles them (sig_fixany_kernel);
+  // whole groups of four: both builds sum alike, model 1
+  const bool tail_ok = dim % 4 != 0 && dim >= 9 && rows_per_band >= 2 && (blas_model == 1 || blas_model == 2);
+  // bands of ONE row: the host calls sdot - modelled for both builds at every length (stage 2: sig_fixany_kernel)
+  const bool one_row_ok = rows_per_band == 1 && (blas_model == 1 || blas_model == 2);
+  if (!tail_ok && !one_row_ok && (blas_model != 1 || dim % 4 != 0)) return LSHRS_E_BADARG;
+  const int body = dim & ~3;
+  if ((dim < 32 && !resident) || (body % 8 != 0 && body > 4096) || counters == nullptr) return LSHRS_E_BADARG;
+  return 0;
+}
+
+// What a split pass of this shape is: its geometry, whether stage 1 is the resident-image kernel, whether the pass takes the
+// input itself (`aligned`) - and what it refuses.  split_pass and lshrs_split_stage2_args (stage 2 alone, for the tests' entry).
+struct SplitPlan { SigGeom g; int row_bytes; bool narrow; SigResident rs; bool aligned; };
+static int split_plan(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands, int32_t rows_per_band, int32_t dim,
+                      const uint8_t* keys, const int64_t* tie_list, int32_t tie_cap, const int32_t* tie_count, const int64_t* flag_list,
+                      int32_t flag_cap, const int32_t* flag_count, int blas_model, SplitPlan* p) {
   if (X == nullptr || workspace == nullptr || keys == nullptr || n < 0 || ldx < dim || flag_list == nullptr ||
       flag_count == nullptr || flag_cap <= 0 || !sig_shape_ok(num_bands, rows_per_band, dim))
     return LSHRS_E_BADARG;
   if (tie_list != nullptr && (tie_count == nullptr || tie_cap < 0)) return LSHRS_E_BADARG;
   const SigGeom g = sig_geom(num_bands, rows_per_band, dim);
-  const int row_bytes = num_bands * g.bb;
   // (the second stage patches key bits with 32-bit atomics on the ALIGNED word around the byte: a word that straddles two
   //  rows, or the end of the buffer, shares its page with a byte that is ours, and the bits that are not ours go back as
   //  they came - key rows of any width, keys at any address)
@@ -87,9 +100,6 @@ static int split_pass(const float* X, int64_t n, int64_t ldx, const void* worksp
   if (!sig_has_split(g) && !narrow && !rs.on) return LSHRS_E_TOOLARGE;
   const int64_t wgs = ((n + 127) / 128 + 7) / 8 * 8 * g.cb;          // (the most any launch below makes)
   if (n >= ((int64_t)1 << 42) || wgs > 0x7fffffffLL || g.cb > 65535) return LSHRS_E_TOOLARGE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const Opts o = read_opts(opts);
-  const float* base = static_cast<const float*>(workspace);
   // (a partial last k-tile - dim % 32 != 0 - only with the replay: its stage 2 is the one that reads the chunks past a row's end as zero)
   // With the replaying stage 2 rows of any length (from 9 elements) at any 4-byte address: both stage-1 kernels fetch the row's
   // last dim % 4 elements with its last four and shift them into place; stage 2 adds the library's scalar tail behind its tiles
@@ -98,6 +108,69 @@ static int split_pass(const float* X, int64_t n, int64_t ldx, const void* worksp
   const bool aligned = ldx < (1 << 20) &&
                        (blas_model != 0 ? (dim % 4 == 0 || dim >= 9) && (dim >= 32 || rs.on)
                                         : dim % 32 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0);
+  *p = SplitPlan{g, num_bands * g.bb, narrow, rs, aligned};
+  return 0;
+}
+
+// BUCKETS (lshrs_sig_sort mode 1): sig16_kernel appends flagged and sampled projections by key column (sig_replay.hip takes
+// them from there): long rows, at most 1024 padded key columns, the replaying stage 2, the caller's scratch given
+static bool split_buckets(const SplitPlan& p, int blas_model, int rows_per_band, const lshrs_sig_sort* sort) {
+  const int padcols_all = p.row_bytes * 8;
+  return !p.rs.on && blas_model != 0 && rows_per_band != 1 && sort != nullptr && sort->mode == 1 && sort->thr != nullptr &&
+         padcols_all <= kSortMaxCols && p.g.ktiles > kFixSlabShort && sort->cap / padcols_all >= 64;
+}
+
+// What stage 2 of a split pass is handed.  sort: the bucket scratch where stage 1 filled it (split_buckets), else NULL.
+static FixArgs split_stage2_args(const float* X, int64_t ldx, int dim, const float* base, const SplitPlan& p, int rows_per_band, uint8_t* keys,
+                                 int64_t* tie_list, int32_t tie_cap, int32_t* tie_count, float tau, const int64_t* flag_list, float* flag_y,
+                                 int32_t flag_cap, const int32_t* flag_count, int blas_model, int32_t* counters, const lshrs_sig_sort* sort,
+                                 const int64_t* audit_list, const float* audit_vals, int audit_n) {
+  const SigGeom& g = p.g;
+  FixArgs f = fix_args_base(X, ldx, dim, base, g, rows_per_band, keys, p.row_bytes, flag_list, flag_count, flag_cap, tau, blas_model);
+  if (p.narrow && !p.rs.on) {      // (the narrow block's own copy of the norms: the same values for every valid column)
+    f.norms = base + sig_narrow_offset_floats(g) + sig_narrow_image_floats(g);
+    if (tau > 0.f) f.tie_coef = f.norms;
+  }
+  f.tie_list = tie_list;
+  f.tie_cap = tie_cap;
+  f.tie_count = tie_count;
+  if (sort != nullptr) {
+    f.sorted_list = sort->list;
+    f.sorted_y = sort->y;
+    f.flag_thr = sort->thr;
+    f.col_count = sort->hist + (size_t)(sort->parity & 1) * kSortMaxCols;
+    f.col_cap = sort->cap / (p.row_bytes * 8);
+  }
+  if (blas_model != 0) {
+    f.tail_model = blas_model;
+    f.tie_list = nullptr;
+    f.flag_y = flag_y;
+    f.partials = counters + LSHRS_SIG_COUNTERS;
+    f.count_ties = 1;
+    f.audit_list = audit_n > 0 ? audit_list : nullptr;
+    f.audit_vals = audit_vals;
+    f.audit_n = audit_n;
+  }
+  return f;
+}
+
+static int split_pass(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands,
+                      int32_t rows_per_band, int32_t dim, uint8_t* keys, int64_t* tie_list, int32_t tie_cap,
+                      int32_t* tie_count, float tau, uint8_t* row_flags, int64_t* flag_list, float* flag_y,
+                      int32_t flag_cap, int32_t* flag_count, float tau1, int blas_model, int32_t* counters,
+                      int32_t* host_counts, const lshrs_sig_audit* audit, const lshrs_sig_opts* opts, void* stream) {
+  if (n == 0) return 0;
+  SplitPlan plan;
+  const int rc0 = split_plan(X, n, ldx, workspace, num_bands, rows_per_band, dim, keys, tie_list, tie_cap, tie_count, flag_list, flag_cap,
+                             flag_count, blas_model, &plan);
+  if (rc0 != 0) return rc0;
+  const SigGeom g = plan.g;
+  const int row_bytes = plan.row_bytes;
+  const bool narrow = plan.narrow, aligned = plan.aligned;
+  const SigResident rs = plan.rs;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const Opts o = read_opts(opts);
+  const float* base = static_cast<const float*>(workspace);
   if (!aligned) {  // the split pass is built for 16-byte chunks of 16-byte aligned rows; anything else takes the f32 pass (same keys)
     if (blas_model != 0) return LSHRS_E_BADARG;   // (the f32 kernel reports ties, it does not resolve them)
     return lshrs_sig_hash_batch_f32(X, n, ldx, workspace, num_bands, rows_per_band, dim, keys, tie_list, tie_cap,
@@ -182,11 +255,8 @@ static int split_pass(const float* X, int64_t n, int64_t ldx, const void* worksp
       audit_n = (int)((units - 1 - a.audit_phase) / div + 1);           // units u < `units` with u % div == phase: every slot is written
     }
   }
-  // BUCKETS (lshrs_sig_sort mode 1): sig16_kernel appends flagged and sampled projections by key column (sig_replay.hip takes
-  // them from there): long rows, at most 1024 padded key columns, the replaying stage 2, the caller's scratch given
   const int padcols_all = row_bytes * 8;
-  const bool buckets = !rs.on && blas_model != 0 && rows_per_band != 1 && o.sort != nullptr && o.sort->mode == 1 && o.sort->thr != nullptr &&
-                       padcols_all <= kSortMaxCols && g.ktiles > kFixSlabShort && o.sort->cap / padcols_all >= 64;
+  const bool buckets = split_buckets(plan, blas_model, rows_per_band, o.sort);
   if (buckets) {
     a.tie_list = o.sort->list;
     a.flag_y = o.sort->y;
@@ -209,31 +279,8 @@ static int split_pass(const float* X, int64_t n, int64_t ldx, const void* worksp
     if (rc != 0) return rc;
   }
   // stage 2: the flagged projections, one by one
-  FixArgs f = fix_args_base(X, ldx, dim, base, g, rows_per_band, keys, row_bytes, flag_list, flag_count, flag_cap, tau, blas_model);
-  if (narrow && !rs.on) {          // (the narrow block's own copy of the norms: the same values for every valid column)
-    f.norms = a.norms;
-    if (tau > 0.f) f.tie_coef = f.norms;
-  }
-  f.tie_list = tie_list;
-  f.tie_cap = tie_cap;
-  f.tie_count = tie_count;
-  if (buckets) {
-    f.sorted_list = o.sort->list;
-    f.sorted_y = o.sort->y;
-    f.flag_thr = o.sort->thr;
-    f.col_count = a.col_count;
-    f.col_cap = a.col_cap;
-  }
-  if (blas_model != 0) {
-    f.tail_model = blas_model;
-    f.tie_list = nullptr;
-    f.flag_y = flag_y;
-    f.partials = counters + LSHRS_SIG_COUNTERS;
-    f.count_ties = 1;
-    f.audit_list = audit_n > 0 ? a.audit_list : nullptr;
-    f.audit_vals = a.audit_vals;
-    f.audit_n = audit_n;
-  }
+  const FixArgs f = split_stage2_args(X, ldx, dim, base, plan, rows_per_band, keys, tie_list, tie_cap, tie_count, tau, flag_list, flag_y,
+                                      flag_cap, flag_count, blas_model, counters, buckets ? o.sort : nullptr, a.audit_list, a.audit_vals, audit_n);
   const int rc2 = lshrs_replay_stage2(f, counters, host_counts, o, s);
   if (rc2 != 0) return rc2;
   return -(int)hipGetLastError();
@@ -254,17 +301,31 @@ int lshrs_sig_hash_batch_split_replay_f32(const float* X, int64_t n, int64_t ldx
                                           float* flag_y, int32_t flag_cap, float tau1, int32_t blas_model,
                                           int32_t* host_counts, const lshrs_sig_audit* audit, const lshrs_sig_opts* opts,
                                           void* stream) {
-  const bool resident = sig_resident(num_bands, rows_per_band, dim).on;
-  // dim % 4 elements of scalar tail: modelled from 9 elements up, model 1 / 2 = how the build compiles them (sig_fixany_kernel);
-  // whole groups of four: both builds sum alike, model 1
-  const bool tail_ok = dim % 4 != 0 && dim >= 9 && rows_per_band >= 2 && (blas_model == 1 || blas_model == 2);
-  // bands of ONE row: the host calls sdot - modelled for both builds at every length (stage 2: sig_fixany_kernel)
-  const bool one_row_ok = rows_per_band == 1 && (blas_model == 1 || blas_model == 2);
-  if (!tail_ok && !one_row_ok && (blas_model != 1 || dim % 4 != 0)) return LSHRS_E_BADARG;
-  const int body = dim & ~3;
-  if ((dim < 32 && !resident) || (body % 8 != 0 && body > 4096) || counters == nullptr) return LSHRS_E_BADARG;
+  const int rc = split_replay_refusal(num_bands, rows_per_band, dim, blas_model, counters);
+  if (rc != 0) return rc;
   return split_pass(X, n, ldx, workspace, num_bands, rows_per_band, dim, keys, nullptr, 0, counters + 0, tau, row_flags,
                     flag_list, flag_y, flag_cap, counters + 1, tau1, blas_model, counters, host_counts, audit, opts, stream);
 }
 
 }  // extern "C"
+
+// Stage 2 of a split replay pass WITHOUT its stage 1, for lshrs_sig_replay_values_f32 (sig_replay.hip): the refusals of
+// lshrs_sig_hash_batch_split_replay_f32 and of split_pass, and the FixArgs split_pass would hand to lshrs_replay_stage2 for a list
+// the caller filled (counters[1]: its length) - or, want_buckets, for the column segments of o.sort, which must then be what
+// split_pass itself would let stage 1 fill (split_buckets), else LSHRS_E_BADARG.  No audit sample.
+int lshrs_split_stage2_args(const float* X, int64_t n, int64_t ldx, const void* workspace, int32_t num_bands, int32_t rows_per_band,
+                            int32_t dim, uint8_t* keys, int32_t* counters, float tau, int64_t* flag_list, float* flag_y, int32_t flag_cap,
+                            int32_t blas_model, const Opts& o, bool want_buckets, FixArgs* out) {
+  const int rc = split_replay_refusal(num_bands, rows_per_band, dim, blas_model, counters);
+  if (rc != 0) return rc;
+  SplitPlan plan;
+  const int rc0 = split_plan(X, n, ldx, workspace, num_bands, rows_per_band, dim, keys, nullptr, 0, counters + 0, flag_list, flag_cap,
+                             counters + 1, blas_model, &plan);
+  if (rc0 != 0) return rc0;
+  if (!plan.aligned) return LSHRS_E_BADARG;
+  const bool buckets = split_buckets(plan, blas_model, rows_per_band, o.sort);
+  if (buckets != want_buckets) return LSHRS_E_BADARG;
+  *out = split_stage2_args(X, ldx, dim, static_cast<const float*>(workspace), plan, rows_per_band, keys, nullptr, 0, counters + 0, tau, flag_list,
+                           flag_y, flag_cap, counters + 1, blas_model, counters, buckets ? o.sort : nullptr, nullptr, nullptr, 0);
+  return 0;
+}

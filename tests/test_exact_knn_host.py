@@ -48,7 +48,7 @@ def test_the_six_entries_are_in_their_header_their_tuple_and_the_library():
         assert name not in _native.EXPORTS
     # the first header and its tuple are what they were
     assert _declared(os.path.join(_native.INCLUDE, "lshrs_hip.h")) == sorted(_native.EXPORTS)
-    assert len(_native.EXPORTS) == 74 == len(set(_native.EXPORTS)) and len(set(_native.EXPORTS_KNN)) == 6
+    assert len(_native.EXPORTS) == 75 == len(set(_native.EXPORTS)) and len(set(_native.EXPORTS_KNN)) == 6
     assert lib.lshrs_abi_version() == 7 == _native.ABI_VERSION
 
 

@@ -41,7 +41,7 @@ def test_the_six_exports_are_in_the_header_the_binding_and_the_library():
         assert re.search(r"\b" + name + r"\(", header), name
         assert name in _native.EXPORTS and name in exported and hasattr(lib, name), name
     assert lib.lshrs_abi_version() == 7 == _native.ABI_VERSION
-    assert len(_native.EXPORTS) == 74 == len(set(_native.EXPORTS))
+    assert len(_native.EXPORTS) == 75 == len(set(_native.EXPORTS))
 
 
 def test_workspace_bytes():
