@@ -14,6 +14,7 @@ from ._config import HashSignatures
 from ._exact import exact_above, exact_knn, exact_pairs_above, exact_top_k, scan_epsilon, scan_max_window
 from ._groups import exact_groups_above, group_pairs, lsh_groups_above
 from ._join import lsh_pairs_above
+from ._knn_join import lsh_knn
 from ._native import NativeLibraryError
 from .bandrows import get_optimal_config
 from .core import LSHRS, lshrs
@@ -28,6 +29,6 @@ __all__ = [
     "rerank_batch", "quantize_rows", "exact_top_k", "exact_above", "exact_pairs_above", "exact_knn", "lsh_pairs_above", "scan_epsilon", "scan_max_window",
     "get_optimal_config", "InMemoryStorage", "BucketOperation", "NativeLibraryError",
     "RedisPackedWriter", "group_by_bucket", "hex_keys", "HostBlasNotRecognised",
-    "DeviceVectors", "group_pairs", "exact_groups_above", "lsh_groups_above",
+    "DeviceVectors", "group_pairs", "exact_groups_above", "lsh_groups_above", "lsh_knn",
 ]
 __version__ = "0.1.0"

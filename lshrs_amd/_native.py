@@ -1,6 +1,7 @@
 """ctypes binding of ``csrc/liblshrs_hip.so`` (the C ABI declared in ``include/lshrs_hip.h``, ``include/lshrs_knn.h`` and
-``include/lshrs_join.h``) and of ``csrc/liblshrs_groups.so`` (``include/lshrs_groups.h``: a library of its own, loaded by
-:func:`load_groups` when the first grouping asks for it).
+``include/lshrs_join.h``), of ``csrc/liblshrs_groups.so`` (``include/lshrs_groups.h``: a library of its own, loaded by
+:func:`load_groups` when the first grouping asks for it) and of ``csrc/liblshrs_graph.so`` (``include/lshrs_graph.h``: a third,
+loaded by :func:`load_graph` when the first neighbour graph asks for it).
 
 There is no CPU implementation behind this module: if the shared library has not
 been built, or the ABI version does not match, loading raises — loudly — and so
@@ -51,9 +52,21 @@ GROUPS_ABI_VERSION = 1       # LSHRS_GROUPS_ABI_VERSION
 CC_ERR_ENDPOINT = 0x1        # LSHRS_CC_ERR_ENDPOINT: an endpoint outside [0, n)
 CC_ERR_CAP = 0x2             # LSHRS_CC_ERR_CAP: a lane passed an iteration cap
 
+# the third library: neighbour lists out of pairs and their best k (csrc/graph.hip, include/lshrs_graph.h) - one unit, no symbol
+# of the other two
+GRAPH_SOURCE = os.path.join(CSRC, "graph.hip")
+# (LSHRS_GRAPH_LIBRARY: load another build of the same ABI instead - the A/B of -DLSHRS_GRAPH_COMBINE, profiles/lsh_knn.json)
+GRAPH_LIBRARY = os.environ.get("LSHRS_GRAPH_LIBRARY") or os.path.join(CSRC, "liblshrs_graph.so")
+GRAPH_ABI_VERSION = 1        # LSHRS_GRAPH_ABI_VERSION
+GRAPH_ERR_ENDPOINT = 0x1     # LSHRS_GRAPH_ERR_ENDPOINT (degree): an endpoint outside [0, n_rows)
+GRAPH_ERR_LOOP = 0x2         # LSHRS_GRAPH_ERR_LOOP (degree): a pair with a == b
+GRAPH_ERR_RANGE = 0x1        # LSHRS_GRAPH_ERR_RANGE (select): a list outside [0, total]
+GRAPH_ERR_ENTRY = 0x2        # LSHRS_GRAPH_ERR_ENTRY (select): an entry outside [0, n_ids)
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 _groups_lib: Optional[ctypes.CDLL] = None
+_graph_lib: Optional[ctypes.CDLL] = None
 
 
 class NativeLibraryError(RuntimeError):
@@ -120,6 +133,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)
             os.replace(GROUPS_LIBRARY + ".tmp", GROUPS_LIBRARY)
+        # the third library, after the second, in the same way
+        if force or not os.path.exists(GRAPH_LIBRARY) or \
+                os.path.getmtime(GRAPH_LIBRARY) < max(os.path.getmtime(p) for p in _sources_of(GRAPH_SOURCE)):
+            cmd = [hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-I" + CSRC, "-shared", GRAPH_SOURCE, "-o", GRAPH_LIBRARY + ".tmp"]
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.run(cmd, check=True)
+            os.replace(GRAPH_LIBRARY + ".tmp", GRAPH_LIBRARY)
         return LIBRARY
 
 
@@ -475,6 +496,59 @@ def load_groups() -> ctypes.CDLL:
         if got != GROUPS_ABI_VERSION:
             raise NativeLibraryError(f"{GROUPS_LIBRARY} has ABI version {got}, expected {GROUPS_ABI_VERSION}; rebuild it")
         _groups_lib = lib
+        return lib
+
+
+# what include/lshrs_graph.h declares: the exports of liblshrs_graph.so, all of them
+EXPORTS_GRAPH = (
+    "lshrs_graph_abi_version",
+    "lshrs_graph_max_list",
+    "lshrs_graph_wave_list",
+    "lshrs_graph_degree_i64",
+    "lshrs_graph_fill_i64",
+    "lshrs_graph_select_f32",
+)
+
+
+def load_graph() -> ctypes.CDLL:
+    """Load the library of the neighbour lists (once).  Raises NativeLibraryError when it is not there; :func:`load` and
+    :func:`load_groups` neither load it nor need it."""
+    global _graph_lib
+    if _graph_lib is not None:
+        return _graph_lib
+    with _lock:
+        if _graph_lib is not None:
+            return _graph_lib
+        if not os.path.exists(GRAPH_LIBRARY):
+            raise NativeLibraryError(
+                f"{GRAPH_LIBRARY} is missing: the HIP extension has not been built "
+                "(run `python -c 'import __graft_entry__ as g; g.build()'`). "
+                "lshrs_amd has no CPU fallback."
+            )
+        import torch  # noqa: F401  (its libamdhip64 first, as in load())
+
+        try:
+            lib = ctypes.CDLL(GRAPH_LIBRARY)
+        except OSError as exc:  # pragma: no cover - environment specific
+            raise NativeLibraryError(f"cannot load {GRAPH_LIBRARY}: {exc}") from exc
+        for name in EXPORTS_GRAPH:
+            if not hasattr(lib, name):
+                raise NativeLibraryError(f"{GRAPH_LIBRARY} does not export {name}; rebuild it")
+        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+        lib.lshrs_graph_abi_version.argtypes, lib.lshrs_graph_abi_version.restype = [], ctypes.c_int
+        lib.lshrs_graph_max_list.argtypes, lib.lshrs_graph_max_list.restype = [], i32
+        lib.lshrs_graph_wave_list.argtypes, lib.lshrs_graph_wave_list.restype = [], i32
+        # (a, b, n_pairs, n_rows, degree, err, stream)
+        lib.lshrs_graph_degree_i64.argtypes, lib.lshrs_graph_degree_i64.restype = [vp, vp, i64, i64, vp, vp, vp], ctypes.c_int
+        # (a, b, n_pairs, n_rows, row_off, cursor, nbr, stream)
+        lib.lshrs_graph_fill_i64.argtypes, lib.lshrs_graph_fill_i64.restype = [vp, vp, i64, i64, vp, vp, vp, vp], ctypes.c_int
+        # (nbr, scores, row_off, n_rows, total, row_ids, n_ids, k, out_ids, out_scores, out_count, err, stream)
+        lib.lshrs_graph_select_f32.argtypes = [vp, vp, vp, i64, i64, vp, i64, i32, vp, vp, vp, vp, vp]
+        lib.lshrs_graph_select_f32.restype = ctypes.c_int
+        got = lib.lshrs_graph_abi_version()
+        if got != GRAPH_ABI_VERSION:
+            raise NativeLibraryError(f"{GRAPH_LIBRARY} has ABI version {got}, expected {GRAPH_ABI_VERSION}; rebuild it")
+        _graph_lib = lib
         return lib
 
 

@@ -838,6 +838,78 @@ class LSHRS:
                 "largest": int(np.diff(offsets).max()) if groups else 0,
                 "truth_largest": int(np.diff(t_offsets).max()) if truth_groups else 0}
 
+    def neighbors(self, top_k: int = 10, *, min_collisions: int = 1, max_bucket: Optional[int] = None, max_pairs: int = 1 << 26,
+                  return_arrays: bool = False):
+        """For every indexed vector the ``top_k`` best of the vectors it shares a bucket with - the k-NN graph the index holds
+        IN ITS BUCKETS, the approximate counterpart of :meth:`neighbors_exact` (``lshrs_amd.lsh_knn``).  The candidates of an
+        id are the ids it forms a candidate pair with as :meth:`pairs_above` defines one (a shared bucket in at least
+        ``min_collisions`` bands; buckets of more than ``max_bucket`` members count in no role); they are reranked with the
+        id's own vector as the query and ordered by descending score, equal scores by ascending id.  For ``min_collisions =
+        1`` and no ``max_bucket`` an id's list is :meth:`neighbors_exact`'s ranking of that id restricted to its candidates,
+        scores bit for bit; an id with fewer than ``top_k`` candidates has a shorter list, one with none an empty one.
+        Returns ``[(id, [(neighbour, score), ...]), ...]`` in ascending order of id, the form of :meth:`neighbors_exact` - or,
+        with ``return_arrays``, ``(ids (n,), neighbors (n, kk), scores (n, kk), counts (n,))`` with ``-1`` / ``NaN`` behind
+        each row's ``counts``.  Nothing is hashed: the candidates come out of the bucket arrays as they stand.  An empty index
+        gives an empty answer.
+
+        The store, the errors, ``max_pairs`` (distinct candidate pairs) and the two snapshots: as for :meth:`pairs_above`.
+        ``last_search_stats`` receives ``buckets``, ``skipped_buckets``, ``raw_pairs``, ``emitted``, ``launches``, ``rows``,
+        ``live``, ``candidates_max``, ``short_rows`` (ids with fewer than ``kk`` candidates), ``long_lists``,
+        ``segments_folded`` and ``fold_ms``."""
+        from ._knn_join import _check_k
+
+        top_k = _check_k(top_k)
+        over, seg, fold, shape, kw = self._join_plan("neighbors", 0.0, min_collisions, max_bucket, max_pairs)
+        if seg is None:                             # (no bucket holds anybody: a segment without buckets - every list is empty)
+            from . import _native
+
+            torch = _native.require_gpu()
+            dev = over._search_snapshot()[0].device
+            seg = (torch.empty(0, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                   torch.empty(0, dtype=torch.int64, device=dev))
+        ids, nbrs, scores, counts = over.lsh_neighbors(top_k, *seg, *shape, **kw)
+        self.last_search_stats = dict(over.last_search_stats)
+        self.last_search_stats.update(fold)
+        if return_arrays:
+            return ids, nbrs, scores, counts
+        with _gc_paused():
+            return [(i, list(zip(nb[:c], sc[:c]))) for i, nb, sc, c in
+                    zip(ids.tolist(), nbrs.tolist(), scores.astype(np.float64).tolist(), counts.tolist())]
+
+    def recall_neighbors(self, top_k: int = 10) -> Dict[str, Any]:
+        """What the LSH k-NN graph finds of the true one, measured: the truth is :meth:`neighbors_exact` ``(top_k)``, what the
+        index finds is :meth:`neighbors` ``(top_k)``.  Returns ``recall`` (the truth's (id, neighbour) entries that are in the
+        found list of the same id / the truth's entries, pooled over the ids; 1.0 when there are none), ``per_row`` (float32,
+        that share id by id in ascending order of id; NaN where an id has no truth), ``truth_entries``, ``found_entries``,
+        ``short_rows`` (ids whose buckets hold fewer than ``kk`` candidates) and ``expected``: the mean over the truth's
+        scores of the collision law :meth:`recall_above` reports (``lshrs_amd._exact.collision_law``; NaN when there is no
+        truth).  An entry is found only under ITS OWN ID: where a truth neighbour ties bit for bit with the ``kk``-th and the
+        found list holds the other id of the tie, the entry counts as missed.  ``last_search_stats`` is that of the
+        :meth:`neighbors` call."""
+        from ._exact import collision_law
+
+        t_ids, t_nbrs, t_scores = self.neighbors_exact(top_k, return_arrays=True)
+        ids, nbrs, _, counts = self.neighbors(top_k, return_arrays=True)
+        if not np.array_equal(t_ids, ids):
+            raise RuntimeError("recall_neighbors: the index changed between its two searches")
+        n, kk = int(t_nbrs.shape[0]), int(t_nbrs.shape[1])
+        hit = np.zeros(n, dtype=np.int64)
+        if n and kk:
+            # (id, neighbour) as one int64 per entry of the found lists - the row's rank above the neighbour's place among all
+            # ids - and the truth's entries looked up among them
+            rank = np.searchsorted(ids, nbrs.clip(min=0))
+            own = np.arange(n, dtype=np.int64)[:, None]
+            found = np.sort((own * n + rank)[nbrs >= 0])
+            want = own * n + np.searchsorted(ids, t_nbrs)
+            at = np.searchsorted(found, want).clip(max=max(0, found.shape[0] - 1))
+            hit = ((found[at] == want) if found.shape[0] else np.zeros_like(want, dtype=bool)).sum(axis=1)
+        truth_entries = n * kk
+        per = (hit / kk).astype(np.float32) if kk else np.full(n, np.nan, dtype=np.float32)
+        return {"recall": int(hit.sum()) / truth_entries if truth_entries else 1.0, "per_row": per,
+                "truth_entries": truth_entries, "found_entries": int(counts.sum()),
+                "short_rows": int(self.last_search_stats.get("short_rows", 0)),
+                "expected": collision_law(t_scores.reshape(-1), self._config["num_bands"], self._config["rows_per_band"])}
+
     def _join_segment(self, dev, band_bytes: int, fold: Dict[str, Any]):
         """The store's bucket arrays as ONE segment on ``dev`` - ``(codes, offsets, members)`` int64 tensors, None for an empty
         index - folded where the store holds several (``_join.fold_segments``) and kept beside the token that came back with the

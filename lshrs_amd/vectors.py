@@ -54,8 +54,8 @@ def check_ids(ids) -> np.ndarray:
 
 
 class RowSearches:
-    """The seven searches over device-resident rows under ids - the route from whatever holds such rows to ``_exact`` /
-    ``_join``.  The holder supplies ``dim``, ``_search_snapshot() -> (rows, row_ids)`` (``row_ids``: the id of every row,
+    """The eight searches over device-resident rows under ids - the route from whatever holds such rows to ``_exact`` /
+    ``_join`` / ``_groups`` / ``_knn_join``.  The holder supplies ``dim``, ``_search_snapshot() -> (rows, row_ids)`` (``row_ids``: the id of every row,
     negative where it has none; None where the id is the row) and ``translate(ids) -> (rows of those ids, ...)``; it
     receives ``last_search_stats``: what the last search that returned did."""
 
@@ -147,6 +147,20 @@ class RowSearches:
         from ._exact import exact_knn
 
         return self._over_rows(exact_knn, k=k, method=method, return_tensors=return_tensors)
+
+    def lsh_neighbors(self, k, codes, offsets, members, num_bands: int, band_bytes: int, *, return_tensors: bool = False,
+                      **kwargs):
+        """For every stored vector the ``k`` best of its bucket mates in ONE bucket segment (``codes``, ``offsets``,
+        ``members``: device int64 tensors, the members being ids of this store), under the caller's ids: ``(ids (n,) int64
+        ascending, neighbors (n, kk) int64, scores (n, kk) float32, counts (n,) int32)`` - :func:`lshrs_amd.lsh_knn` over the
+        row block where it is, the members translated to its rows (``kwargs``: its ``min_collisions``, ``max_bucket``,
+        ``max_pairs``, ``max_raw_pairs``); rows behind ``counts`` are ``-1`` / ``NaN``.  A member without a stored vector raises
+        ``IndexError``.  The rows and the table are two snapshots taken one after the other, without a lock across both.  What
+        the call did is left in ``last_search_stats``."""
+        from ._knn_join import lsh_knn
+
+        return self._over_rows(lsh_knn, k=k, codes=codes, offsets=offsets, members=members, num_bands=num_bands,
+                               band_bytes=band_bytes, return_tensors=return_tensors, **kwargs)
 
 
 class TensorRows(RowSearches):
