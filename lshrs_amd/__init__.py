@@ -16,6 +16,7 @@ from ._groups import exact_groups_above, group_pairs, lsh_groups_above
 from ._join import lsh_pairs_above
 from ._knn_join import lsh_knn
 from ._native import NativeLibraryError
+from ._refine import expand_candidates, graph_edges, refine_knn
 from .bandrows import get_optimal_config
 from .core import LSHRS, lshrs
 from .hasher import HostBlasNotRecognised, LSHHasher
@@ -30,5 +31,6 @@ __all__ = [
     "get_optimal_config", "InMemoryStorage", "BucketOperation", "NativeLibraryError",
     "RedisPackedWriter", "group_by_bucket", "hex_keys", "HostBlasNotRecognised",
     "DeviceVectors", "group_pairs", "exact_groups_above", "lsh_groups_above", "lsh_knn",
+    "refine_knn", "graph_edges", "expand_candidates",
 ]
 __version__ = "0.1.0"

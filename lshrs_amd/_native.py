@@ -1,7 +1,8 @@
 """ctypes binding of ``csrc/liblshrs_hip.so`` (the C ABI declared in ``include/lshrs_hip.h``, ``include/lshrs_knn.h`` and
 ``include/lshrs_join.h``), of ``csrc/liblshrs_groups.so`` (``include/lshrs_groups.h``: a library of its own, loaded by
 :func:`load_groups` when the first grouping asks for it) and of ``csrc/liblshrs_graph.so`` (``include/lshrs_graph.h``: a third,
-loaded by :func:`load_graph` when the first neighbour graph asks for it).
+loaded by :func:`load_graph` when the first neighbour graph asks for it) and of ``csrc/liblshrs_refine.so``
+(``include/lshrs_refine.h``: a fourth, loaded by :func:`load_refine` when the first refinement asks for it).
 
 There is no CPU implementation behind this module: if the shared library has not
 been built, or the ABI version does not match, loading raises — loudly — and so
@@ -63,10 +64,21 @@ GRAPH_ERR_LOOP = 0x2         # LSHRS_GRAPH_ERR_LOOP (degree): a pair with a == b
 GRAPH_ERR_RANGE = 0x1        # LSHRS_GRAPH_ERR_RANGE (select): a list outside [0, total]
 GRAPH_ERR_ENTRY = 0x2        # LSHRS_GRAPH_ERR_ENTRY (select): an entry outside [0, n_ids)
 
+# the fourth library: the edges of a neighbour table and the rows within two steps (csrc/refine.hip, include/lshrs_refine.h) -
+# one unit, no symbol of the other three
+REFINE_SOURCE = os.path.join(CSRC, "refine.hip")
+REFINE_LIBRARY = os.path.join(CSRC, "liblshrs_refine.so")
+REFINE_ABI_VERSION = 1       # LSHRS_REFINE_ABI_VERSION
+REFINE_ERR_OUTSIDE = 0x1     # LSHRS_REFINE_ERR_OUTSIDE (edges): an entry outside [-1, n_rows)
+REFINE_ERR_SELF = 0x2        # LSHRS_REFINE_ERR_SELF (edges): a row that lists itself
+REFINE_ERR_RANGE = 0x1       # LSHRS_REFINE_ERR_RANGE (count, write): a list outside its array, or too short
+REFINE_ERR_ENTRY = 0x2       # LSHRS_REFINE_ERR_ENTRY (count, write): an entry outside [0, n_rows)
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 _groups_lib: Optional[ctypes.CDLL] = None
 _graph_lib: Optional[ctypes.CDLL] = None
+_refine_lib: Optional[ctypes.CDLL] = None
 
 
 class NativeLibraryError(RuntimeError):
@@ -141,6 +153,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)
             os.replace(GRAPH_LIBRARY + ".tmp", GRAPH_LIBRARY)
+        # the fourth library, after the third, in the same way
+        if force or not os.path.exists(REFINE_LIBRARY) or \
+                os.path.getmtime(REFINE_LIBRARY) < max(os.path.getmtime(p) for p in _sources_of(REFINE_SOURCE)):
+            cmd = [hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-I" + CSRC, "-shared", REFINE_SOURCE, "-o", REFINE_LIBRARY + ".tmp"]
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.run(cmd, check=True)
+            os.replace(REFINE_LIBRARY + ".tmp", REFINE_LIBRARY)
         return LIBRARY
 
 
@@ -549,6 +569,60 @@ def load_graph() -> ctypes.CDLL:
         if got != GRAPH_ABI_VERSION:
             raise NativeLibraryError(f"{GRAPH_LIBRARY} has ABI version {got}, expected {GRAPH_ABI_VERSION}; rebuild it")
         _graph_lib = lib
+        return lib
+
+
+# what include/lshrs_refine.h declares: the exports of liblshrs_refine.so, all of them
+EXPORTS_REFINE = (
+    "lshrs_refine_abi_version",
+    "lshrs_refine_wave_set",
+    "lshrs_refine_max_set",
+    "lshrs_refine_edges_i64",
+    "lshrs_refine_expand_count_i64",
+    "lshrs_refine_expand_write_i64",
+)
+
+
+def load_refine() -> ctypes.CDLL:
+    """Load the library of the graph refinement (once).  Raises NativeLibraryError when it is not there; :func:`load`,
+    :func:`load_groups` and :func:`load_graph` neither load it nor need it."""
+    global _refine_lib
+    if _refine_lib is not None:
+        return _refine_lib
+    with _lock:
+        if _refine_lib is not None:
+            return _refine_lib
+        if not os.path.exists(REFINE_LIBRARY):
+            raise NativeLibraryError(
+                f"{REFINE_LIBRARY} is missing: the HIP extension has not been built "
+                "(run `python -c 'import __graft_entry__ as g; g.build()'`). "
+                "lshrs_amd has no CPU fallback."
+            )
+        import torch  # noqa: F401  (its libamdhip64 first, as in load())
+
+        try:
+            lib = ctypes.CDLL(REFINE_LIBRARY)
+        except OSError as exc:  # pragma: no cover - environment specific
+            raise NativeLibraryError(f"cannot load {REFINE_LIBRARY}: {exc}") from exc
+        for name in EXPORTS_REFINE:
+            if not hasattr(lib, name):
+                raise NativeLibraryError(f"{REFINE_LIBRARY} does not export {name}; rebuild it")
+        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+        lib.lshrs_refine_abi_version.argtypes, lib.lshrs_refine_abi_version.restype = [], ctypes.c_int
+        lib.lshrs_refine_wave_set.argtypes, lib.lshrs_refine_wave_set.restype = [], i32
+        lib.lshrs_refine_max_set.argtypes, lib.lshrs_refine_max_set.restype = [], i32
+        # (graph, n_rows, k_in, keep, err, stream)
+        lib.lshrs_refine_edges_i64.argtypes, lib.lshrs_refine_edges_i64.restype = [vp, i64, i32, vp, vp, vp], ctypes.c_int
+        # (nbr, row_off, n_rows, total, max_degree, cand_count, err, stream)
+        lib.lshrs_refine_expand_count_i64.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp]
+        lib.lshrs_refine_expand_count_i64.restype = ctypes.c_int
+        # (nbr, row_off, n_rows, total, max_degree, cand_off, cand, cand_total, err, stream)
+        lib.lshrs_refine_expand_write_i64.argtypes = [vp, vp, i64, i64, i32, vp, vp, i64, vp, vp]
+        lib.lshrs_refine_expand_write_i64.restype = ctypes.c_int
+        got = lib.lshrs_refine_abi_version()
+        if got != REFINE_ABI_VERSION:
+            raise NativeLibraryError(f"{REFINE_LIBRARY} has ABI version {got}, expected {REFINE_ABI_VERSION}; rebuild it")
+        _refine_lib = lib
         return lib
 
 

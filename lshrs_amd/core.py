@@ -839,7 +839,7 @@ class LSHRS:
                 "truth_largest": int(np.diff(t_offsets).max()) if truth_groups else 0}
 
     def neighbors(self, top_k: int = 10, *, min_collisions: int = 1, max_bucket: Optional[int] = None, max_pairs: int = 1 << 26,
-                  return_arrays: bool = False):
+                  return_arrays: bool = False, refine_rounds: int = 0, max_degree: Optional[int] = None):
         """For every indexed vector the ``top_k`` best of the vectors it shares a bucket with - the k-NN graph the index holds
         IN ITS BUCKETS, the approximate counterpart of :meth:`neighbors_exact` (``lshrs_amd.lsh_knn``).  The candidates of an
         id are the ids it forms a candidate pair with as :meth:`pairs_above` defines one (a shared bucket in at least
@@ -855,10 +855,18 @@ class LSHRS:
         The store, the errors, ``max_pairs`` (distinct candidate pairs) and the two snapshots: as for :meth:`pairs_above`.
         ``last_search_stats`` receives ``buckets``, ``skipped_buckets``, ``raw_pairs``, ``emitted``, ``launches``, ``rows``,
         ``live``, ``candidates_max``, ``short_rows`` (ids with fewer than ``kk`` candidates), ``long_lists``,
-        ``segments_folded`` and ``fold_ms``."""
+        ``segments_folded`` and ``fold_ms``.
+
+        ``refine_rounds`` (default 0: the buckets' graph as it is): that many local-join rounds over the graph
+        (``lshrs_amd.refine_knn``) - every id also considers its neighbours' neighbours, and its list becomes
+        :meth:`neighbors_exact`'s ranking of it restricted to the ids within two steps, scores bit for bit; no score of a list
+        ever decreases.  ``max_degree`` (None: no cap): an id with more adjacent ids connects nobody.  ``last_search_stats``
+        then carries the refinement's own under ``"refine"``."""
         from ._knn_join import _check_k
+        from ._refine import check_refine_args
 
         top_k = _check_k(top_k)
+        refine_rounds, max_degree, _ = check_refine_args(refine_rounds, max_degree)
         over, seg, fold, shape, kw = self._join_plan("neighbors", 0.0, min_collisions, max_bucket, max_pairs)
         if seg is None:                             # (no bucket holds anybody: a segment without buckets - every list is empty)
             from . import _native
@@ -870,13 +878,19 @@ class LSHRS:
         ids, nbrs, scores, counts = over.lsh_neighbors(top_k, *seg, *shape, **kw)
         self.last_search_stats = dict(over.last_search_stats)
         self.last_search_stats.update(fold)
+        if refine_rounds:
+            found = ids
+            ids, nbrs, scores, counts = over.refine_neighbors(nbrs, top_k, rounds=refine_rounds, max_degree=max_degree)
+            if not np.array_equal(found, ids):
+                raise RuntimeError("neighbors: the index changed between the buckets' graph and its refinement")
+            self.last_search_stats["refine"] = dict(over.last_search_stats)
         if return_arrays:
             return ids, nbrs, scores, counts
         with _gc_paused():
             return [(i, list(zip(nb[:c], sc[:c]))) for i, nb, sc, c in
                     zip(ids.tolist(), nbrs.tolist(), scores.astype(np.float64).tolist(), counts.tolist())]
 
-    def recall_neighbors(self, top_k: int = 10) -> Dict[str, Any]:
+    def recall_neighbors(self, top_k: int = 10, refine_rounds: int = 0) -> Dict[str, Any]:
         """What the LSH k-NN graph finds of the true one, measured: the truth is :meth:`neighbors_exact` ``(top_k)``, what the
         index finds is :meth:`neighbors` ``(top_k)``.  Returns ``recall`` (the truth's (id, neighbour) entries that are in the
         found list of the same id / the truth's entries, pooled over the ids; 1.0 when there are none), ``per_row`` (float32,
@@ -885,11 +899,14 @@ class LSHRS:
         scores of the collision law :meth:`recall_above` reports (``lshrs_amd._exact.collision_law``; NaN when there is no
         truth).  An entry is found only under ITS OWN ID: where a truth neighbour ties bit for bit with the ``kk``-th and the
         found list holds the other id of the tie, the entry counts as missed.  ``last_search_stats`` is that of the
-        :meth:`neighbors` call."""
+        :meth:`neighbors` call.  ``refine_rounds``: measure :meth:`neighbors` ``(top_k, refine_rounds=refine_rounds)``
+        instead - ``short_rows`` is then the refinement's, ``expected`` stays the law of the buckets alone."""
         from ._exact import collision_law
+        from ._refine import check_refine_args
 
+        check_refine_args(refine_rounds, None)
         t_ids, t_nbrs, t_scores = self.neighbors_exact(top_k, return_arrays=True)
-        ids, nbrs, _, counts = self.neighbors(top_k, return_arrays=True)
+        ids, nbrs, _, counts = self.neighbors(top_k, return_arrays=True, refine_rounds=refine_rounds)
         if not np.array_equal(t_ids, ids):
             raise RuntimeError("recall_neighbors: the index changed between its two searches")
         n, kk = int(t_nbrs.shape[0]), int(t_nbrs.shape[1])
@@ -907,7 +924,7 @@ class LSHRS:
         per = (hit / kk).astype(np.float32) if kk else np.full(n, np.nan, dtype=np.float32)
         return {"recall": int(hit.sum()) / truth_entries if truth_entries else 1.0, "per_row": per,
                 "truth_entries": truth_entries, "found_entries": int(counts.sum()),
-                "short_rows": int(self.last_search_stats.get("short_rows", 0)),
+                "short_rows": int(self.last_search_stats.get("refine", self.last_search_stats).get("short_rows", 0)),
                 "expected": collision_law(t_scores.reshape(-1), self._config["num_bands"], self._config["rows_per_band"])}
 
     def _join_segment(self, dev, band_bytes: int, fold: Dict[str, Any]):

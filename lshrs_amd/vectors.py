@@ -54,8 +54,8 @@ def check_ids(ids) -> np.ndarray:
 
 
 class RowSearches:
-    """The eight searches over device-resident rows under ids - the route from whatever holds such rows to ``_exact`` /
-    ``_join`` / ``_groups`` / ``_knn_join``.  The holder supplies ``dim``, ``_search_snapshot() -> (rows, row_ids)`` (``row_ids``: the id of every row,
+    """The nine searches over device-resident rows under ids - the route from whatever holds such rows to ``_exact`` /
+    ``_join`` / ``_groups`` / ``_knn_join`` / ``_refine``.  The holder supplies ``dim``, ``_search_snapshot() -> (rows, row_ids)`` (``row_ids``: the id of every row,
     negative where it has none; None where the id is the row) and ``translate(ids) -> (rows of those ids, ...)``; it
     receives ``last_search_stats``: what the last search that returned did."""
 
@@ -161,6 +161,18 @@ class RowSearches:
 
         return self._over_rows(lsh_knn, k=k, codes=codes, offsets=offsets, members=members, num_bands=num_bands,
                                band_bytes=band_bytes, return_tensors=return_tensors, **kwargs)
+
+    def refine_neighbors(self, neighbors, k: int = 10, *, rounds: int = 1, max_degree=None, return_tensors: bool = False):
+        """A k-NN graph of the stored vectors made better by its own entries: ``neighbors`` - ``(n, k_in)`` int64 ids, ``-1``
+        for no entry, one row per stored id in ascending order, what :meth:`lsh_neighbors` and :meth:`neighbors` return - after
+        ``rounds`` local-join rounds in which every id also considers its neighbours' neighbours, under the caller's ids:
+        ``(ids (n,) int64 ascending, neighbors (n, kk) int64, scores (n, kk) float32, counts (n,) int32)`` -
+        :func:`lshrs_amd.refine_knn` over the row block where it is (``max_degree``: ids with more adjacent ids connect
+        nobody).  A name without a stored vector raises ``ValueError``.  What the call did is left in ``last_search_stats``."""
+        from ._refine import refine_knn
+
+        return self._over_rows(refine_knn, neighbors=neighbors, k=k, rounds=rounds, max_degree=max_degree,
+                               return_tensors=return_tensors)
 
 
 class TensorRows(RowSearches):
