@@ -89,6 +89,16 @@ def _desc_key(torch, scores):
     return torch.where(torch.isnan(scores), torch.full_like(key, 0xFFFFFFFF), key)
 
 
+def _ragged(torch, begin, lens):
+    """For lists that begin at ``begin`` and hold ``lens`` entries (int64 tensors): ``(slot, at)`` - for every entry of all of
+    them laid end to end, the list it belongs to and its position in the array the lists lie in."""
+    dev = begin.device
+    slot = torch.repeat_interleave(torch.arange(int(begin.shape[0]), dtype=torch.int64, device=dev), lens)
+    first = torch.cumsum(lens, 0) - lens
+    at = begin[slot] + (torch.arange(int(slot.shape[0]), dtype=torch.int64, device=dev) - first[slot])
+    return slot, at
+
+
 def _rank_long(torch, nbr, scores, row_off, row_ids, k: int, rows, out_ids, out_scores, out_count) -> None:
     """The lists of ``rows`` (int64, ascending: those the kernel left at -1) ranked with torch's stable sorts, the way
     ``_exact._judge_pairs`` orders its pairs: ascending id first, then ONE stable sort on {row, key of the score} - every list
@@ -96,9 +106,8 @@ def _rank_long(torch, nbr, scores, row_off, row_ids, k: int, rows, out_ids, out_
     dev = nbr.device
     begin = row_off[rows]
     lens = row_off[rows + 1] - begin
-    slot = torch.repeat_interleave(torch.arange(int(rows.shape[0]), dtype=torch.int64, device=dev), lens)
+    slot, at = _ragged(torch, begin, lens)
     first = torch.cumsum(lens, 0) - lens                         # where every list begins among the gathered entries
-    at = begin[slot] + (torch.arange(int(slot.shape[0]), dtype=torch.int64, device=dev) - first[slot])
     ids, sc = nbr[at], scores[at]
     if row_ids is not None:
         ids = row_ids[ids]
@@ -178,6 +187,23 @@ def _rerank_lists(torch, corpus, nbr, row_off, m: int):
     return scores, err
 
 
+def _best_of_lists(torch, corpus, lists, off, d_ids, kk: int, live_rows, stats: Dict, adjacency_err=None, rerank=None):
+    """The tail of ``lsh_knn`` and of a round of ``refine_knn``: the lists ``lists`` / ``off`` - one per row of ``corpus`` -
+    reranked (:func:`_rerank_lists`), a zero norm refused, the best ``kk`` selected under the ids ``d_ids``
+    (:func:`select_neighbors`, which leaves ``stats["long_lists"]``) and the live rows gathered: ``(neighbors, scores,
+    counts)``.  ONE readback of its own, the rerank's error word; ``adjacency_err`` - the word of the ``pair_adjacency`` that
+    made the lists, where nobody has read it yet - comes in the same transfer and is judged first.  ``rerank``: the caller's
+    own name for :func:`_rerank_lists`, where it has one."""
+    exact, err = (rerank or _rerank_lists)(torch, corpus, lists, off, int(corpus.shape[0]))
+    bits = torch.stack((err[0], (err if adjacency_err is None else adjacency_err)[0])).cpu().tolist()
+    if adjacency_err is not None and int(bits[1]):              # (the emit names rows of the map, a < b: never seen)
+        raise _native.NativeLibraryError("lsh_knn: " + (ENDPOINT_MSG if int(bits[1]) & 1 else LOOP_MSG))
+    if int(bits[0]) & 5:
+        raise ValueError("Cannot normalize zero vector")
+    s_ids, s_scores, s_count = select_neighbors(lists, exact, off, d_ids, kk, stats)
+    return s_ids[live_rows].contiguous(), s_scores[live_rows].contiguous(), s_count[live_rows].contiguous()
+
+
 def lsh_knn(corpus, k: int, codes, offsets, member_rows, num_bands: int, band_bytes: int, *, row_ids=None,
             min_collisions: int = 1, max_bucket: Optional[int] = None, max_pairs: int = 1 << 26,
             max_raw_pairs: int = 1 << 34, return_tensors: bool = False, stats: Optional[Dict] = None):
@@ -243,16 +269,8 @@ def lsh_knn(corpus, k: int, codes, offsets, member_rows, num_bands: int, band_by
                 out["launches"] = plan.launches
             if emitted and kk:
                 nbr, row_off, err = pair_adjacency(pa[:emitted], pb[:emitted], m)
-                exact, err2 = _rerank_lists(torch, corpus, nbr, row_off, m)
-                bits = torch.stack((err[0], err2[0])).cpu().tolist()
-                if int(bits[0]):                    # (the emit names rows of the map, a < b: never seen)
-                    raise _native.NativeLibraryError("lsh_knn: " + (ENDPOINT_MSG if int(bits[0]) & 1 else LOOP_MSG))
-                if int(bits[1]) & 5:
-                    raise ValueError("Cannot normalize zero vector")
                 sel: Dict = {}
-                s_ids, s_scores, s_count = select_neighbors(nbr, exact, row_off, d_ids, kk, sel)
-                neighbors, scores, counts = s_ids[live_rows].contiguous(), s_scores[live_rows].contiguous(), \
-                    s_count[live_rows].contiguous()
+                neighbors, scores, counts = _best_of_lists(torch, corpus, nbr, row_off, d_ids, kk, live_rows, sel, err)
                 lens = torch.diff(row_off)[live_rows]
                 got = torch.stack((lens.max(), (lens < kk).sum())).cpu().tolist() if n else [0, 0]
                 out.update(candidates_max=int(got[0]), short_rows=int(got[1]), long_lists=sel["long_lists"])

@@ -137,30 +137,17 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)
             os.replace(LIBRARY + ".tmp", LIBRARY)
-        # the second library, after the first: its one unit straight into a shared object, by the same rule of staleness
-        if force or not os.path.exists(GROUPS_LIBRARY) or \
-                os.path.getmtime(GROUPS_LIBRARY) < max(os.path.getmtime(p) for p in _sources_of(GROUPS_SOURCE)):
-            cmd = [hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-I" + CSRC, "-shared", GROUPS_SOURCE, "-o", GROUPS_LIBRARY + ".tmp"]
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.run(cmd, check=True)
-            os.replace(GROUPS_LIBRARY + ".tmp", GROUPS_LIBRARY)
-        # the third library, after the second, in the same way
-        if force or not os.path.exists(GRAPH_LIBRARY) or \
-                os.path.getmtime(GRAPH_LIBRARY) < max(os.path.getmtime(p) for p in _sources_of(GRAPH_SOURCE)):
-            cmd = [hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-I" + CSRC, "-shared", GRAPH_SOURCE, "-o", GRAPH_LIBRARY + ".tmp"]
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.run(cmd, check=True)
-            os.replace(GRAPH_LIBRARY + ".tmp", GRAPH_LIBRARY)
-        # the fourth library, after the third, in the same way
-        if force or not os.path.exists(REFINE_LIBRARY) or \
-                os.path.getmtime(REFINE_LIBRARY) < max(os.path.getmtime(p) for p in _sources_of(REFINE_SOURCE)):
-            cmd = [hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-I" + CSRC, "-shared", REFINE_SOURCE, "-o", REFINE_LIBRARY + ".tmp"]
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.run(cmd, check=True)
-            os.replace(REFINE_LIBRARY + ".tmp", REFINE_LIBRARY)
+        # the side libraries, after the first and in their order: each one unit straight into a shared object, by the same
+        # rule of staleness
+        for side in SIDE_LIBRARIES:
+            source, library = side.source(), side.library()
+            if force or not os.path.exists(library) or \
+                    os.path.getmtime(library) < max(os.path.getmtime(p) for p in _sources_of(source)):
+                cmd = [hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-I" + CSRC, "-shared", source, "-o", library + ".tmp"]
+                if verbose:
+                    print(" ".join(cmd))
+                subprocess.run(cmd, check=True)
+                os.replace(library + ".tmp", library)
         return LIBRARY
 
 
@@ -471,159 +458,103 @@ def load() -> ctypes.CDLL:
         return lib
 
 
+class _SideLibrary:
+    """One of the libraries beside the first - one unit, no symbol of another: what it is built from, what it exports and how
+    it is loaded.  Its source, its path, its ABI number and the loaded library are the module's own ``<NAME>_SOURCE``,
+    ``<NAME>_LIBRARY``, ``<NAME>_ABI_VERSION`` and ``_<name>_lib``, read when they are used."""
+
+    def __init__(self, name: str, abi: str, entries: dict):
+        self.name, self.abi, self.entries = name, abi, entries      # entries: export -> (argtypes, restype), all of them
+
+    def source(self) -> str:
+        return globals()[self.name.upper() + "_SOURCE"]
+
+    def library(self) -> str:
+        return globals()[self.name.upper() + "_LIBRARY"]
+
+    def load(self) -> ctypes.CDLL:
+        """Load the library (once).  Raises NativeLibraryError when it is not there."""
+        slot = "_" + self.name + "_lib"
+        if globals()[slot] is not None:
+            return globals()[slot]
+        with _lock:
+            if globals()[slot] is not None:
+                return globals()[slot]
+            path, version = self.library(), globals()[self.name.upper() + "_ABI_VERSION"]
+            if not os.path.exists(path):
+                raise NativeLibraryError(
+                    f"{path} is missing: the HIP extension has not been built "
+                    "(run `python -c 'import __graft_entry__ as g; g.build()'`). "
+                    "lshrs_amd has no CPU fallback."
+                )
+            import torch  # noqa: F401  (its libamdhip64 first, as in load())
+
+            try:
+                lib = ctypes.CDLL(path)
+            except OSError as exc:  # pragma: no cover - environment specific
+                raise NativeLibraryError(f"cannot load {path}: {exc}") from exc
+            for name in self.entries:
+                if not hasattr(lib, name):
+                    raise NativeLibraryError(f"{path} does not export {name}; rebuild it")
+            for name, (argtypes, restype) in self.entries.items():
+                getattr(lib, name).argtypes, getattr(lib, name).restype = argtypes, restype
+            got = getattr(lib, self.abi)()
+            if got != version:
+                raise NativeLibraryError(f"{path} has ABI version {got}, expected {version}; rebuild it")
+            globals()[slot] = lib
+            return lib
+
+
+_vp, _i32, _i64, _int = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int
 # what include/lshrs_groups.h declares: the exports of liblshrs_groups.so, all of them
-EXPORTS_GROUPS = (
-    "lshrs_groups_abi_version",
-    "lshrs_cc_init_i32",
-    "lshrs_cc_hook_i64",
-    "lshrs_cc_flatten_i32",
-)
+_GROUPS = _SideLibrary("groups", "lshrs_groups_abi_version", {
+    "lshrs_groups_abi_version": ([], _int),
+    "lshrs_cc_init_i32": ([_vp, _i64, _vp], _int),                               # (parent, n, stream)
+    "lshrs_cc_hook_i64": ([_vp, _vp, _i64, _vp, _i64, _vp, _vp], _int),          # (a, b, n_edges, parent, n, err, stream)
+    "lshrs_cc_flatten_i32": ([_vp, _i64, _vp, _vp], _int),                       # (parent, n, err, stream)
+})
+# what include/lshrs_graph.h declares: the exports of liblshrs_graph.so, all of them
+_GRAPH = _SideLibrary("graph", "lshrs_graph_abi_version", {
+    "lshrs_graph_abi_version": ([], _int),
+    "lshrs_graph_max_list": ([], _i32),
+    "lshrs_graph_wave_list": ([], _i32),
+    "lshrs_graph_degree_i64": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp], _int),     # (a, b, n_pairs, n_rows, degree, err, stream)
+    # (a, b, n_pairs, n_rows, row_off, cursor, nbr, stream)
+    "lshrs_graph_fill_i64": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp], _int),
+    # (nbr, scores, row_off, n_rows, total, row_ids, n_ids, k, out_ids, out_scores, out_count, err, stream)
+    "lshrs_graph_select_f32": ([_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),
+})
+# what include/lshrs_refine.h declares: the exports of liblshrs_refine.so, all of them
+_REFINE = _SideLibrary("refine", "lshrs_refine_abi_version", {
+    "lshrs_refine_abi_version": ([], _int),
+    "lshrs_refine_wave_set": ([], _i32),
+    "lshrs_refine_max_set": ([], _i32),
+    "lshrs_refine_edges_i64": ([_vp, _i64, _i32, _vp, _vp, _vp], _int),          # (graph, n_rows, k_in, keep, err, stream)
+    # (nbr, row_off, n_rows, total, max_degree, cand_count, err, stream)
+    "lshrs_refine_expand_count_i64": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp], _int),
+    # (nbr, row_off, n_rows, total, max_degree, cand_off, cand, cand_total, err, stream)
+    "lshrs_refine_expand_write_i64": ([_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp], _int),
+})
+SIDE_LIBRARIES = (_GROUPS, _GRAPH, _REFINE)                # in the order build() makes them
+EXPORTS_GROUPS, EXPORTS_GRAPH, EXPORTS_REFINE = tuple(_GROUPS.entries), tuple(_GRAPH.entries), tuple(_REFINE.entries)
 
 
 def load_groups() -> ctypes.CDLL:
     """Load the library of the connected components (once).  Raises NativeLibraryError when it is not there; :func:`load`
     neither loads it nor needs it."""
-    global _groups_lib
-    if _groups_lib is not None:
-        return _groups_lib
-    with _lock:
-        if _groups_lib is not None:
-            return _groups_lib
-        if not os.path.exists(GROUPS_LIBRARY):
-            raise NativeLibraryError(
-                f"{GROUPS_LIBRARY} is missing: the HIP extension has not been built "
-                "(run `python -c 'import __graft_entry__ as g; g.build()'`). "
-                "lshrs_amd has no CPU fallback."
-            )
-        import torch  # noqa: F401  (its libamdhip64 first, as in load())
-
-        try:
-            lib = ctypes.CDLL(GROUPS_LIBRARY)
-        except OSError as exc:  # pragma: no cover - environment specific
-            raise NativeLibraryError(f"cannot load {GROUPS_LIBRARY}: {exc}") from exc
-        for name in EXPORTS_GROUPS:
-            if not hasattr(lib, name):
-                raise NativeLibraryError(f"{GROUPS_LIBRARY} does not export {name}; rebuild it")
-        vp, i64 = ctypes.c_void_p, ctypes.c_int64
-        lib.lshrs_groups_abi_version.argtypes, lib.lshrs_groups_abi_version.restype = [], ctypes.c_int
-        # (parent, n, stream)
-        lib.lshrs_cc_init_i32.argtypes, lib.lshrs_cc_init_i32.restype = [vp, i64, vp], ctypes.c_int
-        # (a, b, n_edges, parent, n, err, stream)
-        lib.lshrs_cc_hook_i64.argtypes, lib.lshrs_cc_hook_i64.restype = [vp, vp, i64, vp, i64, vp, vp], ctypes.c_int
-        # (parent, n, err, stream)
-        lib.lshrs_cc_flatten_i32.argtypes, lib.lshrs_cc_flatten_i32.restype = [vp, i64, vp, vp], ctypes.c_int
-        got = lib.lshrs_groups_abi_version()
-        if got != GROUPS_ABI_VERSION:
-            raise NativeLibraryError(f"{GROUPS_LIBRARY} has ABI version {got}, expected {GROUPS_ABI_VERSION}; rebuild it")
-        _groups_lib = lib
-        return lib
-
-
-# what include/lshrs_graph.h declares: the exports of liblshrs_graph.so, all of them
-EXPORTS_GRAPH = (
-    "lshrs_graph_abi_version",
-    "lshrs_graph_max_list",
-    "lshrs_graph_wave_list",
-    "lshrs_graph_degree_i64",
-    "lshrs_graph_fill_i64",
-    "lshrs_graph_select_f32",
-)
+    return _GROUPS.load()
 
 
 def load_graph() -> ctypes.CDLL:
     """Load the library of the neighbour lists (once).  Raises NativeLibraryError when it is not there; :func:`load` and
     :func:`load_groups` neither load it nor need it."""
-    global _graph_lib
-    if _graph_lib is not None:
-        return _graph_lib
-    with _lock:
-        if _graph_lib is not None:
-            return _graph_lib
-        if not os.path.exists(GRAPH_LIBRARY):
-            raise NativeLibraryError(
-                f"{GRAPH_LIBRARY} is missing: the HIP extension has not been built "
-                "(run `python -c 'import __graft_entry__ as g; g.build()'`). "
-                "lshrs_amd has no CPU fallback."
-            )
-        import torch  # noqa: F401  (its libamdhip64 first, as in load())
-
-        try:
-            lib = ctypes.CDLL(GRAPH_LIBRARY)
-        except OSError as exc:  # pragma: no cover - environment specific
-            raise NativeLibraryError(f"cannot load {GRAPH_LIBRARY}: {exc}") from exc
-        for name in EXPORTS_GRAPH:
-            if not hasattr(lib, name):
-                raise NativeLibraryError(f"{GRAPH_LIBRARY} does not export {name}; rebuild it")
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        lib.lshrs_graph_abi_version.argtypes, lib.lshrs_graph_abi_version.restype = [], ctypes.c_int
-        lib.lshrs_graph_max_list.argtypes, lib.lshrs_graph_max_list.restype = [], i32
-        lib.lshrs_graph_wave_list.argtypes, lib.lshrs_graph_wave_list.restype = [], i32
-        # (a, b, n_pairs, n_rows, degree, err, stream)
-        lib.lshrs_graph_degree_i64.argtypes, lib.lshrs_graph_degree_i64.restype = [vp, vp, i64, i64, vp, vp, vp], ctypes.c_int
-        # (a, b, n_pairs, n_rows, row_off, cursor, nbr, stream)
-        lib.lshrs_graph_fill_i64.argtypes, lib.lshrs_graph_fill_i64.restype = [vp, vp, i64, i64, vp, vp, vp, vp], ctypes.c_int
-        # (nbr, scores, row_off, n_rows, total, row_ids, n_ids, k, out_ids, out_scores, out_count, err, stream)
-        lib.lshrs_graph_select_f32.argtypes = [vp, vp, vp, i64, i64, vp, i64, i32, vp, vp, vp, vp, vp]
-        lib.lshrs_graph_select_f32.restype = ctypes.c_int
-        got = lib.lshrs_graph_abi_version()
-        if got != GRAPH_ABI_VERSION:
-            raise NativeLibraryError(f"{GRAPH_LIBRARY} has ABI version {got}, expected {GRAPH_ABI_VERSION}; rebuild it")
-        _graph_lib = lib
-        return lib
-
-
-# what include/lshrs_refine.h declares: the exports of liblshrs_refine.so, all of them
-EXPORTS_REFINE = (
-    "lshrs_refine_abi_version",
-    "lshrs_refine_wave_set",
-    "lshrs_refine_max_set",
-    "lshrs_refine_edges_i64",
-    "lshrs_refine_expand_count_i64",
-    "lshrs_refine_expand_write_i64",
-)
+    return _GRAPH.load()
 
 
 def load_refine() -> ctypes.CDLL:
     """Load the library of the graph refinement (once).  Raises NativeLibraryError when it is not there; :func:`load`,
     :func:`load_groups` and :func:`load_graph` neither load it nor need it."""
-    global _refine_lib
-    if _refine_lib is not None:
-        return _refine_lib
-    with _lock:
-        if _refine_lib is not None:
-            return _refine_lib
-        if not os.path.exists(REFINE_LIBRARY):
-            raise NativeLibraryError(
-                f"{REFINE_LIBRARY} is missing: the HIP extension has not been built "
-                "(run `python -c 'import __graft_entry__ as g; g.build()'`). "
-                "lshrs_amd has no CPU fallback."
-            )
-        import torch  # noqa: F401  (its libamdhip64 first, as in load())
-
-        try:
-            lib = ctypes.CDLL(REFINE_LIBRARY)
-        except OSError as exc:  # pragma: no cover - environment specific
-            raise NativeLibraryError(f"cannot load {REFINE_LIBRARY}: {exc}") from exc
-        for name in EXPORTS_REFINE:
-            if not hasattr(lib, name):
-                raise NativeLibraryError(f"{REFINE_LIBRARY} does not export {name}; rebuild it")
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        lib.lshrs_refine_abi_version.argtypes, lib.lshrs_refine_abi_version.restype = [], ctypes.c_int
-        lib.lshrs_refine_wave_set.argtypes, lib.lshrs_refine_wave_set.restype = [], i32
-        lib.lshrs_refine_max_set.argtypes, lib.lshrs_refine_max_set.restype = [], i32
-        # (graph, n_rows, k_in, keep, err, stream)
-        lib.lshrs_refine_edges_i64.argtypes, lib.lshrs_refine_edges_i64.restype = [vp, i64, i32, vp, vp, vp], ctypes.c_int
-        # (nbr, row_off, n_rows, total, max_degree, cand_count, err, stream)
-        lib.lshrs_refine_expand_count_i64.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp]
-        lib.lshrs_refine_expand_count_i64.restype = ctypes.c_int
-        # (nbr, row_off, n_rows, total, max_degree, cand_off, cand, cand_total, err, stream)
-        lib.lshrs_refine_expand_write_i64.argtypes = [vp, vp, i64, i64, i32, vp, vp, i64, vp, vp]
-        lib.lshrs_refine_expand_write_i64.restype = ctypes.c_int
-        got = lib.lshrs_refine_abi_version()
-        if got != REFINE_ABI_VERSION:
-            raise NativeLibraryError(f"{REFINE_LIBRARY} has ABI version {got}, expected {REFINE_ABI_VERSION}; rebuild it")
-        _refine_lib = lib
-        return lib
+    return _REFINE.load()
 
 
 class SigOpts(ctypes.Structure):

@@ -12,7 +12,7 @@ expand     ``lshrs_refine_expand_count_i64``, ``torch.cumsum``, ``lshrs_refine_e
            PARTICULAR ORDER.
 rerank     ``_knn_join._rerank_lists``: row ``r`` as the float32 query of its own list, the orientation of ``exact_knn``.
 select     ``_knn_join.select_neighbors``: per row the best ``k`` by (score descending, id ascending) - independent of the
-           order the expansion left.
+           order the expansion left.  (Both through ``_knn_join._best_of_lists``, the tail ``lsh_knn`` ends in.)
 
 No CPU compute path: the host checks arguments, reads counts and error words back, and keeps statistics.
 """
@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _native
 from ._exact import _finish, _live_by_id, _rows_args
-from ._knn_join import _check_k, _rerank_lists, pair_adjacency, select_neighbors
+from ._knn_join import _best_of_lists, _check_k, _ragged, _rerank_lists, pair_adjacency
 from .similarity import _on_device, corpus_suffix
 
 __all__ = ["refine_knn", "graph_edges", "expand_candidates", "refine_wave_set", "refine_max_set"]
@@ -79,16 +79,6 @@ def graph_edges(graph):
         _native.check(lib.lshrs_refine_edges_i64(graph.data_ptr(), n_rows, k_in, keep.data_ptr(), err.data_ptr(),
                                                  torch.cuda.current_stream(dev).cuda_stream), "lshrs_refine_edges_i64")
     return keep, err
-
-
-def _ragged(torch, begin, lens):
-    """For lists that begin at ``begin`` and hold ``lens`` entries (int64 tensors): ``(slot, at)`` - for every entry of all of
-    them laid end to end, the list it belongs to and its position in the array the lists lie in."""
-    dev = begin.device
-    slot = torch.repeat_interleave(torch.arange(int(begin.shape[0]), dtype=torch.int64, device=dev), lens)
-    first = torch.cumsum(lens, 0) - lens
-    at = begin[slot] + (torch.arange(int(slot.shape[0]), dtype=torch.int64, device=dev) - first[slot])
-    return slot, at
 
 
 def _expand_with_torch(torch, nbr, row_off, rows, cap: Optional[int]):
@@ -276,12 +266,8 @@ def refine_knn(corpus, neighbors, k: int, *, row_ids=None, rounds: int = 1, max_
                                  f"theirs")
             lens = torch.diff(cand_off)[live_rows]
             if entries:
-                exact, err3 = _rerank_lists(torch, corpus, cand, cand_off, m)
-                if int(err3[0].item()) & 5:
-                    raise ValueError("Cannot normalize zero vector")
-                s_ids, s_scores, s_count = select_neighbors(cand, exact, cand_off, d_ids, kk, did)
-                neighbors_out, scores_out, counts_out = s_ids[live_rows].contiguous(), s_scores[live_rows].contiguous(), \
-                    s_count[live_rows].contiguous()
+                neighbors_out, scores_out, counts_out = _best_of_lists(torch, corpus, cand, cand_off, d_ids, kk, live_rows, did,
+                                                                       rerank=_rerank_lists)
             got = torch.stack((lens.max(), (lens < kk).sum(), (neighbors_out != before).any(dim=1).sum())).cpu().tolist()
             for name in per_round if rounds else ():
                 out[name].append({"entries": entries, "candidates_max": int(got[0]), "changed_rows": int(got[2])}.get(

@@ -9,34 +9,23 @@
 //             answer does not depend on the order fill left.
 //
 // The library stands alone: no symbol of liblshrs_hip.so or liblshrs_groups.so.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "lshrs_graph.h"
+#include "lshrs_lists.h"
 #include "lshrs_rows.h"
 
 namespace {
 
-using lshrs::desc_key;
+using namespace lshrs;                             // (lshrs_lists.h: the layers shared with refine, groups and join; desc_key)
 
-constexpr int kThreads = 256;                      // four wave64 per workgroup
 constexpr int64_t kMaxCount = 0x7fffffffLL;        // rows and pairs: a degree is an int32
 constexpr int kWaveList = 256;                     // the longest list one wave sorts: 4 KiB of LDS per wave, 16 KiB per workgroup
 constexpr int kMaxList = 4096;                     // the longest list a workgroup sorts: 64 KiB, two workgroups per CU
-constexpr int kWavesPerGroup = kThreads / 64;
 constexpr int kLongBlocksPerCu = 2;
 constexpr uint32_t kNanBits = 0x7fc00000u;
 #ifndef LSHRS_GRAPH_COMBINE
 #define LSHRS_GRAPH_COMBINE 0
 #endif
 constexpr bool kCombine = LSHRS_GRAPH_COMBINE != 0;   // equal addresses of a wave combined before the atomic (see reserve)
-
-// the bits of a wave's lanes or-ed into err by one lane; every lane of the wave calls it
-__device__ __forceinline__ void report(int32_t* err, int bad) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) bad |= __shfl_xor(bad, off);
-  if ((threadIdx.x & 63) == 0 && bad) atomicOr(err, bad);
-}
 
 // One unit added to counter[row] for every lane that is `active`; each such lane gets the value its own unit found there.
 // Every lane of the wave calls it.  Plain: one atomicAdd per lane.  COMBINE: the lanes that name the same row are found round
@@ -52,12 +41,12 @@ __device__ __forceinline__ int reserve(int32_t* counter, int64_t row, bool activ
     const int leader = __ffsll((unsigned long long)todo) - 1;
     const int64_t named = __shfl(row, leader);
     const bool mine = active && row == named;
-    const uint64_t group = __ballot(mine);
+    const Places group = places_of(mine);         // (its leader is `leader`: the first lane waiting holds the row it names)
     int base = 0;
-    if (lane == leader) base = atomicAdd(counter + row, (int)__popcll(group));
+    if (lane == leader) base = atomicAdd(counter + row, group.count());
     base = __shfl(base, leader);
-    if (mine) slot = base + (int)__popcll(group & ((1ull << lane) - 1ull));
-    todo &= ~group;
+    if (mine) slot = base + group.rank();
+    todo &= ~group.flagged;
   }
   return slot;
 }
@@ -132,19 +121,6 @@ __device__ __forceinline__ int64_t item_id(const Item& x) {
 }
 __device__ __forceinline__ bool behind(const Item& x, const Item& y) { return x.hi > y.hi || (x.hi == y.hi && x.lo > y.lo); }
 
-// What the threads of a network wait with between two passes.  A wave on its own slice of LDS needs no barrier: its LDS
-// instructions execute in order; the fences keep the compiler from moving a pass's reads above the stores before it.
-template <bool WAVE>
-__device__ __forceinline__ void pass_done() {
-  if (WAVE) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  } else {
-    __syncthreads();
-  }
-}
-
 // The ascending bitonic network over items[0, n), n a power of two, by THREADS threads of which this is thread t.
 template <int THREADS, bool WAVE>
 __device__ __forceinline__ void sort_items(Item* items, int n, int t) {
@@ -178,17 +154,6 @@ struct SelectArgs {
   int32_t* err;
 };
 
-// The list of a row: where it begins and how long it is; a list that does not lie within [0, total] is empty and reported.
-__device__ __forceinline__ int64_t list_of(const SelectArgs& s, int64_t row, int64_t& begin, int& bad) {
-  begin = s.row_off[row];
-  const int64_t end = s.row_off[row + 1];
-  if (begin < 0 || end < begin || end > s.total) {
-    bad |= LSHRS_GRAPH_ERR_RANGE;
-    begin = 0;
-    return 0;
-  }
-  return end - begin;
-}
 
 // One list of `len` <= the network's capacity, by THREADS threads (this one: t): loaded as items, sorted, the best
 // min(k, len) written out and the tail padded.
@@ -241,51 +206,39 @@ __global__ __launch_bounds__(kThreads) void select_wave_kernel(SelectArgs s) {
   int bad = 0;
   if (row < s.n_rows) {               // (uniform in the wave)
     int64_t begin;
-    const int64_t len = list_of(s, row, begin, bad);
+    const int64_t len = list_of(s, row, begin, bad, LSHRS_GRAPH_ERR_RANGE);
     if (len <= kWaveList) select_list<64, true>(s, slices[wave], row, begin, (int)len, lane, bad);
   }
   report(s.err, bad);
 }
 
-// Longer lists: the workgroups walk the rows 256 at a time - a thread looks at one row and notes it where it is long - and
-// sort the noted rows one after the other.  A list beyond kMaxList gets its -1 and nothing else.
+// Longer lists: the workgroups walk the rows (walk_rows) - a thread notes its row where its list is long - and sort the noted
+// rows one after the other.  A list beyond kMaxList gets its -1 and nothing else.
 __global__ __launch_bounds__(kThreads) void select_long_kernel(SelectArgs s) {
   extern __shared__ __attribute__((aligned(16))) unsigned char graph_lds[];
-  Item* items = reinterpret_cast<Item*>(graph_lds);
-  int* noted = reinterpret_cast<int*>(graph_lds + (size_t)kMaxList * sizeof(Item));     // [kThreads] and their number
-  int* n_noted = noted + kThreads;
+  int* noted = reinterpret_cast<int*>(graph_lds + (size_t)kMaxList * sizeof(Item));     // (walk_rows: the noted rows)
   int bad = 0;
-  for (int64_t base = (int64_t)blockIdx.x * kThreads; base < s.n_rows; base += (int64_t)gridDim.x * kThreads) {
-    if (threadIdx.x == 0) *n_noted = 0;
-    __syncthreads();
-    const int64_t mine = base + threadIdx.x;
-    if (mine < s.n_rows) {
-      int64_t begin;
-      int unused = 0;                 // (a list out of range is the wave kernel's to report)
-      if (list_of(s, mine, begin, unused) > kWaveList) noted[atomicAdd(n_noted, 1)] = threadIdx.x;
-    }
-    __syncthreads();
-    const int todo = *n_noted;
-    for (int j = 0; j < todo; ++j) {
-      const int64_t row = base + noted[j];
-      int64_t begin;
-      int unused = 0;
-      const int64_t len = list_of(s, row, begin, unused);
-      if (len > kMaxList) {
-        if (threadIdx.x == 0) s.out_count[row] = -1;
-      } else {
-        select_list<kThreads, false>(s, items, row, begin, (int)len, threadIdx.x, bad);
-      }
-    }
-    __syncthreads();                  // (noted[] is read: the next 256 rows may be noted)
-  }
+  walk_rows<kThreads, false>(
+      s, noted,
+      [](const SelectArgs& s, int64_t row, int&) {
+        int64_t begin;
+        int unused = 0;               // (a list out of range is the wave kernel's to report)
+        return list_of(s, row, begin, unused, LSHRS_GRAPH_ERR_RANGE) > kWaveList;
+      },
+      [&bad](const SelectArgs& s, int64_t row, int) {
+        int64_t begin;
+        int unused = 0;
+        const int64_t len = list_of(s, row, begin, unused, LSHRS_GRAPH_ERR_RANGE);
+        if (len > kMaxList) {
+          if (threadIdx.x == 0) s.out_count[row] = -1;
+        } else {
+          select_list<kThreads, false>(s, reinterpret_cast<Item*>(graph_lds), row, begin, (int)len, threadIdx.x, bad);
+        }
+      });
   report(s.err, bad);
 }
 
-constexpr size_t kLongLds = (size_t)kMaxList * sizeof(Item) + (kThreads + 4) * sizeof(int);
-
-inline bool usable(const void* p, uintptr_t align) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & (align - 1)) == 0; }
-inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+constexpr size_t kLongLds = (size_t)kMaxList * sizeof(Item) + (kWalkInts<kThreads, false> + 3) * sizeof(int);
 
 }  // namespace
 
@@ -327,20 +280,8 @@ int lshrs_graph_select_f32(const int64_t* nbr, const float* scores, const int64_
     return LSHRS_E_BADARG;
   if (total > 0 && (!usable(nbr, 8) || !usable(scores, 4))) return LSHRS_E_BADARG;
   if (row_ids != nullptr && !usable(row_ids, 8)) return LSHRS_E_BADARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int device = 0, cus = 0;
-  hipError_t rc = hipGetDevice(&device);
-  if (rc == hipSuccess) rc = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-  if (rc == hipSuccess)
-    rc = hipFuncSetAttribute(reinterpret_cast<const void*>(select_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)kLongLds);
-  if (rc != hipSuccess) return -(int)rc;
   const SelectArgs args{nbr, scores, row_off, n_rows, total, row_ids, n_ids, k, out_ids, out_scores, out_count, err};
-  hipLaunchKernelGGL(select_wave_kernel, dim3(blocks_for(n_rows, kWavesPerGroup)), dim3(kThreads), 0, s, args);
-  const int64_t resident = (int64_t)(cus > 0 ? cus : 1) * kLongBlocksPerCu, wanted = (n_rows + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(select_long_kernel, dim3((unsigned)(wanted < resident ? wanted : resident)), dim3(kThreads), kLongLds, s,
-                     args);
-  return -(int)hipGetLastError();
+  return launch_tiers(select_wave_kernel, select_long_kernel, args, n_rows, kLongLds, kLongBlocksPerCu, stream);
 }
 
 }  // extern "C"

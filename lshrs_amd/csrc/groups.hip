@@ -11,14 +11,13 @@
 // are those bounds plus a constant, and a lane that passes one reports it (err bit 1) and leaves.  Inside hook and flatten
 // every access to `parent` is an agent-scope relaxed atomic: the L2 of an XCD is not coherent with the others', and a stale
 // value - an earlier ancestor - costs steps, never the result.  The library stands alone: no symbol of liblshrs_hip.so.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "lshrs_groups.h"
+#include "lshrs_lists.h"
 
 namespace {
 
-constexpr int kThreads = 256;                      // four wave64 per workgroup
+using namespace lshrs;                             // (lshrs_lists.h: the layers shared with graph, refine and join)
+
 constexpr int kBlocksPerCu = 8;                    // 2048 lanes per CU: every wave slot of its SIMDs
 constexpr int64_t kMaxVertices = 0x7fffffffLL;     // a vertex is an int32
 constexpr int64_t kCapSlack = 16;
@@ -29,13 +28,6 @@ __device__ __forceinline__ int32_t ld(const int32_t* parent, int64_t x) {
 }
 __device__ __forceinline__ void st(int32_t* parent, int64_t x, int32_t v) {
   __hip_atomic_store(parent + x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the bits of a wave's lanes or-ed into err by one lane; every lane of the wave calls it
-__device__ __forceinline__ void report(int32_t* err, int bad) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) bad |= __shfl_xor(bad, off);
-  if ((threadIdx.x & 63) == 0 && bad) atomicOr(err, bad);
 }
 
 // A vertex that was the root of x's tree when its entry was read, by a walk with path halving: parent[x] = its grandparent,
@@ -117,9 +109,6 @@ __global__ __launch_bounds__(kThreads) void cc_flatten_kernel(int32_t* parent, i
   report(err, bad);
 }
 
-inline bool usable(const void* p, uintptr_t align) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & (align - 1)) == 0; }
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
 }  // namespace
 
 extern "C" {
@@ -131,7 +120,7 @@ int lshrs_cc_init_i32(int32_t* parent, int64_t n, void* stream) {
   if (n > kMaxVertices) return LSHRS_E_TOOLARGE;
   if (n == 0) return 0;
   if (!usable(parent, 4)) return LSHRS_E_BADARG;
-  hipLaunchKernelGGL(cc_init_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), parent, n);
+  hipLaunchKernelGGL(cc_init_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), parent, n);
   return -(int)hipGetLastError();
 }
 
@@ -141,12 +130,9 @@ int lshrs_cc_hook_i64(const int64_t* a, const int64_t* b, int64_t n_edges, int32
   if (n > kMaxVertices) return LSHRS_E_TOOLARGE;
   if (n == 0 || n_edges == 0) return 0;
   if (!usable(a, 8) || !usable(b, 8) || !usable(parent, 4) || !usable(err, 4)) return LSHRS_E_BADARG;
-  int device = 0, cus = 0;
-  hipError_t rc = hipGetDevice(&device);
-  if (rc == hipSuccess) rc = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+  unsigned blocks = 0;
+  const hipError_t rc = resident_grid(blocks_for(n_edges, kThreads), kBlocksPerCu, blocks);
   if (rc != hipSuccess) return -(int)rc;
-  const int64_t resident = (int64_t)(cus > 0 ? cus : 1) * kBlocksPerCu, wanted = (n_edges + kThreads - 1) / kThreads;
-  const unsigned blocks = (unsigned)(wanted < resident ? wanted : resident);
   hipLaunchKernelGGL(cc_hook_kernel, dim3(blocks), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a, b, n_edges, parent, n,
                      err);
   return -(int)hipGetLastError();
@@ -157,7 +143,7 @@ int lshrs_cc_flatten_i32(int32_t* parent, int64_t n, int32_t* err, void* stream)
   if (n > kMaxVertices) return LSHRS_E_TOOLARGE;
   if (n == 0) return 0;
   if (!usable(parent, 4) || !usable(err, 4)) return LSHRS_E_BADARG;
-  hipLaunchKernelGGL(cc_flatten_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), parent, n, err);
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), parent, n, err);
   return -(int)hipGetLastError();
 }
 

@@ -15,8 +15,15 @@
 // Every loop is bounded by its iteration count; no workgroup waits for another.
 #include "lshrs_common.h"
 #include "lshrs_join.h"
+#include "lshrs_lists.h"
 
 namespace {
+
+using lshrs::blocks_for;
+using lshrs::places_of;
+using lshrs::Places;
+using lshrs::report;
+using lshrs::usable;
 
 constexpr int kJoinThreads = 256;
 constexpr int64_t kJoinMaxLanes = 0x7fffffffLL * kJoinThreads;      // what a one-dimensional grid of 256-lane workgroups covers
@@ -71,9 +78,7 @@ __global__ __launch_bounds__(kJoinThreads) void join_rowmap_kernel(const int64_t
       }
     }
   }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) bad |= __shfl_xor(bad, off);
-  if ((threadIdx.x & 63) == 0 && bad) atomicOr(err, bad);
+  report(err, bad);
 }
 
 // W: int32 per load of a map row - 4 where num_bands is a multiple of 4 (every row then starts at a 16-byte boundary), 2
@@ -128,13 +133,13 @@ __global__ __launch_bounds__(kJoinThreads) void join_emit_kernel(const int64_t* 
     }
   }
   // the wave reserves the slots of its hits with one add on the cursor (which counts what does not fit, too)
-  const unsigned long long mask = __ballot(hit);
-  if (mask == 0ull) return;
-  const int leader = __ffsll((long long)mask) - 1;
+  const Places hits = places_of(hit);
+  if (hits.flagged == 0ull) return;
+  const int leader = hits.leader();
   unsigned long long first_slot = 0ull;
-  if (lane == leader) first_slot = atomicAdd(total, (unsigned long long)__popcll(mask));
+  if (lane == leader) first_slot = atomicAdd(total, (unsigned long long)hits.count());
   first_slot = __shfl(first_slot, leader);
-  const int64_t slot = (int64_t)first_slot + __popcll(mask & ((1ull << lane) - 1ull));
+  const int64_t slot = (int64_t)first_slot + hits.rank();
   if (hit && slot < capacity) {
     out_a[slot] = a;
     out_b[slot] = b;
@@ -142,8 +147,6 @@ __global__ __launch_bounds__(kJoinThreads) void join_emit_kernel(const int64_t* 
   }
 }
 
-inline bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kJoinThreads - 1) / kJoinThreads); }
 
 }  // namespace
 
@@ -161,11 +164,8 @@ int lshrs_join_rowmap_i64(const int64_t* codes, const int64_t* offsets, int64_t 
                           int32_t* err, void* stream) {
   if (n_codes < 0 || n_members < 0 || n_rows < 0 || band_bytes < 1 || band_bytes > 6 || num_bands < 1 || max_bucket < 2)
     return LSHRS_E_BADARG;
-  if (workspace == nullptr || err == nullptr || !aligned_to(workspace, 16) || !aligned_to(err, 4)) return LSHRS_E_BADARG;
-  if (n_codes > 0 && n_members > 0 &&
-      (codes == nullptr || offsets == nullptr || member_rows == nullptr || !aligned_to(codes, 8) || !aligned_to(offsets, 8) ||
-       !aligned_to(member_rows, 8)))
-    return LSHRS_E_BADARG;
+  if (!usable(workspace, 16) || !usable(err, 4)) return LSHRS_E_BADARG;
+  if (n_codes > 0 && n_members > 0 && (!usable(codes, 8) || !usable(offsets, 8) || !usable(member_rows, 8))) return LSHRS_E_BADARG;
   if (n_codes > kJoinMaxBuckets || n_rows > kJoinMaxBuckets || n_rows * (int64_t)num_bands > kJoinMaxCells || n_members > kJoinMaxLanes)
     return LSHRS_E_TOOLARGE;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -175,7 +175,7 @@ int lshrs_join_rowmap_i64(const int64_t* codes, const int64_t* offsets, int64_t 
     if (rc != hipSuccess) return -(int)rc;
   }
   if (n_codes == 0 || n_members == 0) return 0;
-  hipLaunchKernelGGL(join_rowmap_kernel, dim3(blocks_for(n_members)), dim3(kJoinThreads), 0, s, codes, offsets, n_codes,
+  hipLaunchKernelGGL(join_rowmap_kernel, dim3(blocks_for(n_members, kJoinThreads)), dim3(kJoinThreads), 0, s, codes, offsets, n_codes,
                      8 * band_bytes, (int)num_bands, member_rows, n_members, n_rows, max_bucket, static_cast<int32_t*>(workspace), err);
   return -(int)hipGetLastError();
 }
@@ -187,18 +187,14 @@ int lshrs_join_emit_i64(const int64_t* offsets, const int64_t* pair_prefix, int6
   if (n_codes < 0 || n_rows < 0 || num_bands < 1 || raw_begin < 0 || raw_count < 0 || capacity < 0 || min_collisions < 1 ||
       min_collisions > num_bands)
     return LSHRS_E_BADARG;
-  if (total == nullptr || !aligned_to(total, 8)) return LSHRS_E_BADARG;
-  if (capacity > 0 && (out_a == nullptr || out_b == nullptr || out_hits == nullptr || !aligned_to(out_a, 8) ||
-                       !aligned_to(out_b, 8) || !aligned_to(out_hits, 4)))
-    return LSHRS_E_BADARG;
+  if (!usable(total, 8)) return LSHRS_E_BADARG;
+  if (capacity > 0 && (!usable(out_a, 8) || !usable(out_b, 8) || !usable(out_hits, 4))) return LSHRS_E_BADARG;
   if (n_codes > kJoinMaxBuckets || n_rows > kJoinMaxBuckets || n_rows * (int64_t)num_bands > kJoinMaxCells || raw_count > kJoinMaxRaw)
     return LSHRS_E_TOOLARGE;
   if (n_codes == 0 || raw_count == 0) return 0;
-  if (offsets == nullptr || pair_prefix == nullptr || member_rows == nullptr || workspace == nullptr || !aligned_to(offsets, 8) ||
-      !aligned_to(pair_prefix, 8) || !aligned_to(member_rows, 8) || !aligned_to(workspace, 16))
-    return LSHRS_E_BADARG;
+  if (!usable(offsets, 8) || !usable(pair_prefix, 8) || !usable(member_rows, 8) || !usable(workspace, 16)) return LSHRS_E_BADARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(blocks_for(raw_count)), block(kJoinThreads);
+  const dim3 grid(blocks_for(raw_count, kJoinThreads)), block(kJoinThreads);
   const int32_t* map = static_cast<const int32_t*>(workspace);
   unsigned long long* cursor = reinterpret_cast<unsigned long long*>(total);
   if (num_bands % 4 == 0)

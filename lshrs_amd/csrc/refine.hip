@@ -10,16 +10,14 @@
 //             the lanes won in.
 //
 // The library stands alone: no symbol of liblshrs_hip.so, liblshrs_groups.so or liblshrs_graph.so.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+#include "lshrs_lists.h"
 #include "lshrs_refine.h"
 
 namespace {
 
-constexpr int kThreads = 256;                      // four wave64 per workgroup
+using namespace lshrs;                             // (lshrs_lists.h: the layers shared with graph, groups and join)
+
 constexpr int64_t kMaxCount = 0x7fffffffLL;        // rows, and entries of a table: a member of a set is an int32
-constexpr int kWavesPerGroup = kThreads / 64;
 constexpr int kWaveSet = 1024;                     // the largest bound one wave takes: 2048 slots, 8 KiB per wave, 32 KiB per workgroup
 constexpr int kMaxSet = 8192;                      // the largest bound a workgroup takes: 16384 slots, 64 KiB, two workgroups per CU
 constexpr int kWaveSlots = 2 * kWaveSet;
@@ -28,13 +26,6 @@ constexpr int kMinSlots = 64;
 constexpr int kSub = 16;                           // the lanes that share one midpoint's list: four midpoints per wave at a time
 constexpr int kLongBlocksPerCu = 2;
 constexpr int kEmpty = -1;                         // (no row is negative)
-
-// the bits of a wave's lanes or-ed into err by one lane; every lane of the wave calls it
-__device__ __forceinline__ void report(int32_t* err, int bad) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) bad |= __shfl_xor(bad, off);
-  if ((threadIdx.x & 63) == 0 && bad) atomicOr(err, bad);
-}
 
 __global__ __launch_bounds__(kThreads) void edges_kernel(const int64_t* __restrict__ graph, int64_t n_rows, int k_in,
                                                          uint8_t* __restrict__ keep, int32_t* err) {
@@ -78,18 +69,6 @@ struct ExpandArgs {
   int32_t* err;
 };
 
-// The list of a row: where it begins and how long it is; a list that does not lie within [0, total] is empty and reported.
-__device__ __forceinline__ int64_t list_of(const ExpandArgs& s, int64_t row, int64_t& begin, int& bad) {
-  begin = s.row_off[row];
-  const int64_t end = s.row_off[row + 1];
-  if (begin < 0 || end < begin || end > s.total) {
-    bad |= LSHRS_REFINE_ERR_RANGE;
-    begin = 0;
-    return 0;
-  }
-  return end - begin;
-}
-
 // What the entry m of a list adds to its row's bound: the length of m's own list where m is a midpoint - a row, with a list
 // inside nbr, at or under the cap - and where that list begins; else 0.
 __device__ __forceinline__ int64_t midpoint_of(const ExpandArgs& s, int64_t m, int64_t& begin, int& bad) {
@@ -98,7 +77,7 @@ __device__ __forceinline__ int64_t midpoint_of(const ExpandArgs& s, int64_t m, i
     bad |= LSHRS_REFINE_ERR_ENTRY;
     return 0;
   }
-  const int64_t len = list_of(s, m, begin, bad);
+  const int64_t len = list_of(s, m, begin, bad, LSHRS_REFINE_ERR_RANGE);
   return (s.max_degree > 0 && len > s.max_degree) ? 0 : len;
 }
 
@@ -118,19 +97,6 @@ __device__ __forceinline__ int64_t bound_by_wave(const ExpandArgs& s, int64_t be
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) sum += __shfl_xor(sum, off);
   return deg + sum;
-}
-
-// What the threads of a row wait with between clearing its set and filling it.  A wave on its own slice of LDS needs no barrier:
-// its LDS instructions execute in order; the fences keep the compiler from moving accesses across.
-template <bool WAVE>
-__device__ __forceinline__ void pass_done() {
-  if (WAVE) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  } else {
-    __syncthreads();
-  }
 }
 
 // v into the set of mask + 1 slots: true where THIS lane put it there, false where it was there already.  At most
@@ -178,16 +144,15 @@ __device__ __forceinline__ void expand_row(const ExpandArgs& s, int* table, int*
   int found = 0;                      // WAVE: the rows found so far, the same in every lane
   // the lanes of this wave whose v is new: each gets a place in the list, and writes v there in the write launch
   auto emit = [&](bool fresh, int64_t v) {
-    const uint64_t won = __ballot(fresh);
-    if (!won) return;
-    const int before = (int)__popcll(won & ((1ull << lane) - 1ull));
+    const Places won = places_of(fresh);
+    if (!won.flagged) return;
+    const int before = won.rank();
     int base = found;
     if (WAVE) {
-      found += (int)__popcll(won);
+      found += won.count();
     } else {
-      const int leader = __ffsll((unsigned long long)won) - 1;
-      if (lane == leader) base = atomicAdd(counter, (int)__popcll(won));
-      base = __shfl(base, leader);
+      if (lane == won.leader()) base = atomicAdd(counter, won.count());
+      base = __shfl(base, won.leader());
     }
     if (fresh && writing) {
       if (base + before < room) s.cand[out + base + before] = v;
@@ -234,7 +199,7 @@ __global__ __launch_bounds__(kThreads) void expand_wave_kernel(ExpandArgs s) {
   int bad = 0;
   if (row < s.n_rows) {               // (uniform in the wave)
     int64_t begin;
-    const int64_t deg = list_of(s, row, begin, bad);
+    const int64_t deg = list_of(s, row, begin, bad, LSHRS_REFINE_ERR_RANGE);
     if (deg <= kWaveSet) {
       const int64_t bound = bound_by_wave(s, begin, deg, lane, bad);
       if (bound <= kWaveSet) expand_row<64, true>(s, slices[wave], nullptr, row, begin, (int)deg, (int)bound, lane, bad);
@@ -243,68 +208,39 @@ __global__ __launch_bounds__(kThreads) void expand_wave_kernel(ExpandArgs s) {
   report(s.err, bad);
 }
 
-// Rows beyond: the workgroups walk the rows 256 at a time - a thread bounds one row and notes it where it is the workgroup's -
-// and expand the noted rows one after the other.  A row beyond kMaxSet gets its -1 in the count launch and nothing else.
+// Rows beyond: the workgroups walk the rows (walk_rows) - a thread bounds one row and notes it, with its bound, where it is the
+// workgroup's - and expand the noted rows one after the other.  A row beyond kMaxSet gets its -1 in the count launch and
+// nothing else.
 __global__ __launch_bounds__(kThreads) void expand_long_kernel(ExpandArgs s) {
   extern __shared__ __attribute__((aligned(16))) unsigned char refine_lds[];
-  int* table = reinterpret_cast<int*>(refine_lds);
-  int* noted = table + kMaxSlots;     // [kThreads], the bounds of the noted [kThreads], their number, the counter of a row
-  int* noted_bound = noted + kThreads;
-  int* n_noted = noted_bound + kThreads;
-  int* counter = n_noted + 1;
-  int bad = 0;
-  for (int64_t base = (int64_t)blockIdx.x * kThreads; base < s.n_rows; base += (int64_t)gridDim.x * kThreads) {
-    if (threadIdx.x == 0) *n_noted = 0;
-    __syncthreads();
-    const int64_t mine = base + threadIdx.x;
-    if (mine < s.n_rows) {
-      int64_t begin;
-      int unused = 0;                 // (a list out of range is the wave kernel's to report)
-      const int64_t deg = list_of(s, mine, begin, unused);
-      const int64_t bound = deg > kMaxSet ? deg : bound_by_lane(s, begin, deg);
-      if (bound > kMaxSet) {
-        if (s.cand_off == nullptr) s.cand_count[mine] = -1;
-      } else if (bound > kWaveSet) {
-        const int at = atomicAdd(n_noted, 1);
-        noted[at] = threadIdx.x;
-        noted_bound[at] = (int)bound;
-      }
-    }
-    __syncthreads();
-    const int todo = *n_noted;
-    for (int j = 0; j < todo; ++j) {
-      const int64_t row = base + noted[j];
-      int64_t begin;
-      int unused = 0;
-      const int64_t deg = list_of(s, row, begin, unused);
-      expand_row<kThreads, false>(s, table, counter, row, begin, (int)deg, noted_bound[j], threadIdx.x, bad);
-    }
-    __syncthreads();                  // (noted[] is read: the next 256 rows may be noted)
-  }
+  int* noted = reinterpret_cast<int*>(refine_lds) + kMaxSlots;     // behind the table: walk_rows' noted rows and their bounds,
+  int bad = 0;                                                     // and behind them the counter of a row
+  walk_rows<kThreads, true>(
+      s, noted,
+      [](const ExpandArgs& s, int64_t row, int& bound_of) {
+        int64_t begin;
+        int unused = 0;               // (a list out of range is the wave kernel's to report)
+        const int64_t deg = list_of(s, row, begin, unused, LSHRS_REFINE_ERR_RANGE);
+        const int64_t bound = deg > kMaxSet ? deg : bound_by_lane(s, begin, deg);
+        if (bound > kMaxSet) {
+          if (s.cand_off == nullptr) s.cand_count[row] = -1;
+          return false;
+        }
+        bound_of = (int)bound;
+        return bound > kWaveSet;
+      },
+      [&bad](const ExpandArgs& s, int64_t row, int bound) {
+        int* table = reinterpret_cast<int*>(refine_lds);
+        int64_t begin;
+        int unused = 0;
+        const int64_t deg = list_of(s, row, begin, unused, LSHRS_REFINE_ERR_RANGE);
+        expand_row<kThreads, false>(s, table, table + kMaxSlots + kWalkInts<kThreads, true>, row, begin, (int)deg, bound,
+                                    threadIdx.x, bad);
+      });
   report(s.err, bad);
 }
 
-constexpr size_t kLongLds = (size_t)kMaxSlots * sizeof(int) + (2 * kThreads + 4) * sizeof(int);
-
-inline bool usable(const void* p, uintptr_t align) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & (align - 1)) == 0; }
-inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
-// both launches of the expansion: the wave kernel over all rows, the workgroup kernel on a grid sized to the device
-int launch_expand(const ExpandArgs& args, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int device = 0, cus = 0;
-  hipError_t rc = hipGetDevice(&device);
-  if (rc == hipSuccess) rc = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-  if (rc == hipSuccess)
-    rc = hipFuncSetAttribute(reinterpret_cast<const void*>(expand_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)kLongLds);
-  if (rc != hipSuccess) return -(int)rc;
-  hipLaunchKernelGGL(expand_wave_kernel, dim3(blocks_for(args.n_rows, kWavesPerGroup)), dim3(kThreads), 0, s, args);
-  const int64_t resident = (int64_t)(cus > 0 ? cus : 1) * kLongBlocksPerCu, wanted = (args.n_rows + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(expand_long_kernel, dim3((unsigned)(wanted < resident ? wanted : resident)), dim3(kThreads), kLongLds, s,
-                     args);
-  return -(int)hipGetLastError();
-}
+constexpr size_t kLongLds = (size_t)kMaxSlots * sizeof(int) + (kWalkInts<kThreads, true> + 3) * sizeof(int);
 
 }  // namespace
 
@@ -331,7 +267,8 @@ int lshrs_refine_expand_count_i64(const int64_t* nbr, const int64_t* row_off, in
   if (n_rows == 0) return 0;
   if (!usable(row_off, 8) || !usable(cand_count, 4) || !usable(err, 4)) return LSHRS_E_BADARG;
   if (total > 0 && !usable(nbr, 8)) return LSHRS_E_BADARG;
-  return launch_expand(ExpandArgs{nbr, row_off, n_rows, total, max_degree, cand_count, nullptr, nullptr, 0, err}, stream);
+  const ExpandArgs args{nbr, row_off, n_rows, total, max_degree, cand_count, nullptr, nullptr, 0, err};
+  return launch_tiers(expand_wave_kernel, expand_long_kernel, args, n_rows, kLongLds, kLongBlocksPerCu, stream);
 }
 
 int lshrs_refine_expand_write_i64(const int64_t* nbr, const int64_t* row_off, int64_t n_rows, int64_t total, int32_t max_degree,
@@ -342,7 +279,8 @@ int lshrs_refine_expand_write_i64(const int64_t* nbr, const int64_t* row_off, in
   if (!usable(row_off, 8) || !usable(cand_off, 8) || !usable(err, 4)) return LSHRS_E_BADARG;
   if (total > 0 && !usable(nbr, 8)) return LSHRS_E_BADARG;
   if (cand_total > 0 && !usable(cand, 8)) return LSHRS_E_BADARG;
-  return launch_expand(ExpandArgs{nbr, row_off, n_rows, total, max_degree, nullptr, cand_off, cand, cand_total, err}, stream);
+  const ExpandArgs args{nbr, row_off, n_rows, total, max_degree, nullptr, cand_off, cand, cand_total, err};
+  return launch_tiers(expand_wave_kernel, expand_long_kernel, args, n_rows, kLongLds, kLongBlocksPerCu, stream);
 }
 
 }  // extern "C"

@@ -286,3 +286,58 @@ def test_select_reports_what_it_does_not_read():
     ids, sc, count, err, clean = _select(lists, scores, row_ids, 3, row_off=[5, 0, 2])
     assert count.tolist() == [0, 2] and ids[1].tolist() == [103, 104, -1]
     del rng
+
+
+# ------------------------------------------------------------------------------------------
+# select: the workgroup tier's walk over the rows (lshrs_lists.h: walk_rows) beyond its first window
+# ------------------------------------------------------------------------------------------
+def _check_rows(got, lists, scores, row_ids, k, rows):
+    """Rows `rows` of a _select answer against tests/_knn_join_reference.rank_list, bit for bit."""
+    from tests._knn_join_reference import rank_list
+
+    got_ids, got_scores, got_count = got[:3]
+    for r in rows:
+        want = rank_list(list(zip(row_ids[lists[r]].tolist(), scores[r].tolist())), k)
+        assert got_count[r] == len(want), r
+        assert got_ids[r].tolist() == [e[0] for e in want] + [-1] * (k - len(want)), r
+        assert np.array_equal(got_scores[r, :len(want)].view(np.uint32), np.array([e[1] for e in want], np.float32).view(np.uint32)), r
+        assert np.all(got_scores[r, len(want):].view(np.uint32) == 0x7FC00000), r
+
+
+def test_select_walks_every_window_of_the_rows():
+    """600 rows - two full windows of 256 and a ragged third: workgroup lists at both ends of every window, three of them and
+    one beyond the limit noted in window 0, every other list empty or short."""
+    lib = _lib()                        # (first: without the library nothing below is worth making)
+    wave, longest = lib.lshrs_graph_wave_list(), lib.lshrs_graph_max_list()
+    n, k, over = 600, 10, 50
+    lengths = [r % 5 for r in range(n)]
+    for r in (0, 7, 100, 255, 256, 511, 512, 599):
+        lengths[r] = wave + 1
+    lengths[over] = longest + 1
+    rng = np.random.default_rng(600)
+    row_ids = ((1 << 40) + 3 * rng.permutation(N_IDS)).astype(np.int64)
+    lists = [rng.choice(N_IDS, size=c, replace=False).astype(np.int64) for c in lengths]
+    scores = [_contents("nan" if r % 2 else "distinct", c, rng) for r, c in enumerate(lengths)]
+    got = _select(lists, scores, row_ids, k)
+    assert got[3] == 0 and got[4]
+    assert got[2][over] == -1 and np.all(got[0][over] == -9) and np.all(got[1][over] == 77.0)
+    _check_rows(got, lists, scores, row_ids, k, [r for r in range(n) if r != over])
+
+
+def test_select_comes_round_to_a_workgroup_s_second_window():
+    """2 x 256 x CUs + 257 rows: one window more than the resident grid of the workgroup kernel has workgroups, and a ragged
+    one behind it - all rows empty but the last, whose list is the workgroup's."""
+    import torch
+
+    lib = _lib()                        # (first: without the library nothing below is worth making)
+    wave = lib.lshrs_graph_wave_list()
+    n = 2 * 256 * torch.cuda.get_device_properties(0).multi_processor_count + 257
+    rng = np.random.default_rng(257)
+    row_ids = ((1 << 40) + 3 * rng.permutation(N_IDS)).astype(np.int64)
+    none = np.zeros(0, np.int64)
+    lists = [none] * (n - 1) + [rng.choice(N_IDS, size=wave + 1, replace=False).astype(np.int64)]
+    scores = [none.astype(np.float32)] * (n - 1) + [_contents("distinct", wave + 1, rng)]
+    got = _select(lists, scores, row_ids, 1)
+    assert got[3] == 0 and got[4]
+    assert np.all(got[2][:n - 1] == 0) and np.all(got[0][:n - 1] == -1) and np.all(got[1][:n - 1].view(np.uint32) == 0x7FC00000)
+    _check_rows(got, lists, scores, row_ids, 1, [n - 1])

@@ -316,3 +316,52 @@ def test_offsets_that_do_not_belong_set_the_bit_and_nothing_leaves_the_arrays():
     assert err & 1 and clean
     for r in range(150):
         assert sorted(cand[good[r]:good[r + 1]].tolist()) == sorted(want[r]), r
+
+
+# ------------------------------------------------------------------------------------------
+# expand: the workgroup tier's walk over the rows (lshrs_lists.h: walk_rows) beyond its first window
+# ------------------------------------------------------------------------------------------
+def _check_expansion(count, got, want, rows):
+    for r in rows:
+        assert count[r] == len(want[r]) and len(set(got[r])) == len(got[r]) and set(got[r]) == want[r], r
+
+
+def test_expand_walks_every_window_of_the_rows():
+    """Rows 0 .. 599 - two full windows of 256 and a third: workgroup rows at both ends of each, three of them and one beyond
+    the limit noted in window 0, every other row empty.  A workgroup row's list is wave_set + 1 DISTINCT rows with empty lists,
+    the row beyond's max_set + 1 of them: 600 rows cannot hold those, so max_set + 1 empty rows stand behind the 600 - and behind
+    them one more workgroup row, the last of a ragged window."""
+    lib = _lib()                        # (first: without the library nothing below is worth making)
+    wave, most = lib.lshrs_refine_wave_set(), lib.lshrs_refine_max_set()
+    n, over = 600 + most + 2, 50
+    assert n % 256
+    lists = [[] for _ in range(n)]
+    for r in (0, 7, 100, 255, 256, 511, 512, 599, n - 1):
+        lists[r] = list(range(600 + r % 97, 600 + r % 97 + wave + 1))
+    lists[over] = list(range(600, 600 + most + 1))
+    bounds = bound_reference(lists)
+    assert sorted(set(bounds)) == [0, wave + 1, most + 1] and max(map(max, (x for x in lists if x))) < n - 1
+    want = expand_reference(lists)
+    count, got, err, clean = _expand_at_the_abi(lists)
+    assert err == 0 and clean
+    assert count[over] == -1 and got[over] == []
+    _check_expansion(count, got, want, [r for r in range(n) if r != over])
+
+
+def test_expand_comes_round_to_a_workgroup_s_second_window():
+    """2 x 256 x CUs + 257 rows: one window more than the resident grid of the workgroup kernel has workgroups, and a ragged
+    one behind it - all rows empty but the last, which is the workgroup's."""
+    import torch
+
+    lib = _lib()                        # (first: without the library nothing below is worth making)
+    wave = lib.lshrs_refine_wave_set()
+    n = 2 * 256 * torch.cuda.get_device_properties(0).multi_processor_count + 257
+    own = list(range(1000, 1000 + wave + 1))
+    nbr, off = np.array(own, dtype=np.int64), np.r_[np.zeros(n, np.int64), len(own)]
+    small = [own] + [[]] * (1000 + wave + 1)           # (the reference of the one row, on a table it fits in)
+    want = expand_reference(small)[0]
+    assert bound_reference(small)[0] == wave + 1 and len(want) == len(own)
+    count, err, clean = _count(nbr, off, n)
+    assert err == 0 and clean and np.all(count[:n - 1] == 0) and count[n - 1] == len(want)
+    cand, err, clean = _write(nbr, off, n, np.r_[np.zeros(n, np.int64), len(own)])
+    assert err == 0 and clean and len(cand) == len(want) and set(cand.tolist()) == want

@@ -94,7 +94,7 @@ def test_build_makes_the_fourth_library_with_its_header_s_entries_and_nothing_of
     assert _exported(_native.GRAPH_LIBRARY) == set(_native.EXPORTS_GRAPH)
     # fresh: nothing is compiled again
     deps = _native._sources_of(_native.REFINE_SOURCE)
-    assert {os.path.basename(p) for p in deps} == {"refine.hip", "lshrs_refine.h", "lshrs_hip.h"}
+    assert {os.path.basename(p) for p in deps} == {"refine.hip", "lshrs_refine.h", "lshrs_hip.h", "lshrs_lists.h"}
     before = os.path.getmtime(path)
     _native.build()
     assert os.path.getmtime(path) == before and not os.path.exists(path + ".tmp")
